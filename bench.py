@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - advection hot path (dense LK + semi-Lagrangian) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is
 already resident in HBM: motion estimate from the input frames (dense
@@ -43,6 +43,8 @@ MU_SOURCES = ("pysteps_amd/csrc/steps_loop.hip", "pysteps_amd/csrc/fft.hip", "py
               "pysteps_amd/csrc/mask.hip", "pysteps_amd/csrc/cascade.hip", "pysteps_amd/csrc/common.h")
 LK_SOURCES = ("pysteps_amd/csrc/lk.hip", "pysteps_amd/csrc/lk_sparse.hip", "pysteps_amd/csrc/sparse_qc.hip",
               "pysteps_amd/csrc/idw.hip", "pysteps_amd/csrc/dense_lk.hip", "pysteps_amd/csrc/common.h")
+DUMP_BYTES = 64 * 10**6  # what --dump-outputs may write in all
+DUMP_SEED = 0
 
 
 def blob_hash(relpath):
@@ -89,7 +91,13 @@ def parse_args():
     ap.add_argument("--no-steps-stock", action="store_true", help="skip the sampled stock nowcasts.steps run (oracle/_ref) of steps_e2e")
     ap.add_argument("--advection-only", action="store_true",
                     help="N > 1: time the member advection alone (the SL-only surrogate of rounds 1-2) instead of the member loop")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="N = 1 workload: write what the last timed step returned (motion field, extrapolated fields) as "
+                         "DIR/<name>.npy; arrays over their share of %d bytes are written as a fixed, seeded sample" % DUMP_BYTES)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Dist:
@@ -790,8 +798,29 @@ def time_steps(step, dist, steps, warmup, events=None):
     return dist.max(time.perf_counter() - t0)
 
 
+def dump_outputs(out_dir, arrays):
+    """Write the device arrays `arrays` ({name: DeviceArray}, float32 or float64) as out_dir/<name>.npy in their own
+    dtype.  An array larger than its share of DUMP_BYTES is written as a 1-d array of its values at a sample of flat
+    indices (sorted, drawn with DUMP_SEED): the same positions in every run with the same arguments, so that the
+    files of two builds can be compared element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 4096  # room for the .npy header
+    for name, arr in arrays.items():
+        if arr.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s" % (name, arr.dtype))
+        # pageable host memory: the pinned pool the later legs of the line use stays as it was
+        host = arr.to_host(out=np.empty(arr.shape, arr.dtype))
+        if host.nbytes > share:
+            rng = np.random.default_rng(DUMP_SEED)
+            host = host.reshape(-1)[np.unique(rng.integers(0, host.size, share // host.itemsize))]
+        np.save(os.path.join(out_dir, name + ".npy"), host)
+
+
 def main():
     args = parse_args()
+    if args.dump_outputs and (args.workload != "default" or args.force_members_path
+                              or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        sys.exit("--dump-outputs: only the N = 1 workload (LK + semilag of one field) writes its outputs")
     dist = Dist(args.gpus)
     os.environ.setdefault("PYSTEPS_HIP_DEVICE", str(dist.local_rank))
 
@@ -834,6 +863,8 @@ def main():
         if i is not None:
             ev[i][1].record()
             counter["i"] = i + 1
+            if args.dump_outputs and i + 1 == args.steps:  # what the caller of the last timed step receives
+                counter["last"] = {"motion_field": v, "extrapolated": out} if have_lk else {"extrapolated": out}
         return out
 
     for _ in range(args.warmup):
@@ -848,6 +879,8 @@ def main():
     dist.barrier()
     elapsed = dist.max(time.perf_counter() - t0)
     counter["i"] = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, counter.pop("last"))
 
     sl_ms = sum(a.elapsed_ms(b) for a, b in ev) / args.steps
     ms_per_step = elapsed / args.steps * 1e3

@@ -2,8 +2,10 @@
 
 * the two known-answer tests of pysteps/tests/test_extrapolation_semilagrangian.py:9-24,57-72
 * golden vectors produced by the unmodified reference (tools/make_golden.py)
-* if /root/reference is present (build container), a live comparison as well
+* the reference's outputs for two more field / motion pairs (tests/golden/semilag_oracle_pins.npz)
 """
+
+import os
 
 import numpy as np
 import pytest
@@ -11,9 +13,8 @@ from numpy.testing import assert_array_almost_equal
 
 from oracle import semilag as osl
 from oracle import semilag_cport as ocl
-from tools import ref_loader
 
-from conftest import nan_mismatch
+from conftest import GOLDEN, nan_mismatch
 
 GOLDEN_SL = [
     "sl_int_T6", "sl_shear_K3", "sl_K0", "sl_list_vt", "sl_nan_min", "sl_nan_nan",
@@ -23,6 +24,11 @@ GOLDEN_SL = [
     "sl_velnan", "sl_velnan_K3_nanfield", "sl_velnan_K0_o0", "sl_velnan_min",
 ]
 BOUNDARY_MODES = ["constant", "nearest", "reflect", "mirror", "wrap", "grid-constant", "grid-wrap"]
+
+
+@pytest.fixture(scope="module")
+def semilag_pins():
+    return np.load(os.path.join(GOLDEN, "semilag_oracle_pins.npz"), allow_pickle=False)
 
 
 def _kat_inputs(speed):
@@ -169,16 +175,11 @@ def test_chained_calls_equal_one_call():
     assert np.array_equal(d, dfull)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
-def test_oracle_matches_live_reference():
-    ref = ref_loader.load("pysteps.extrapolation.semilagrangian")
-    rng = np.random.default_rng(11)
-    m, n = 50, 70
-    p = rng.gamma(1.0, 2.0, (m, n)).astype(np.float32)
-    y, x = np.mgrid[0:m, 0:n]
-    v = np.stack([3 + 0.08 * (y - m / 2), -2 + 0.06 * (x - n / 2)]).astype(np.float32)
+def test_oracle_matches_live_reference(semilag_pins):
+    """Both oracles against the reference's outputs for a sheared field at n_iter 0 / 1 / 2 (tools/make_golden.py)."""
+    p, v = semilag_pins["shear/precip"], semilag_pins["shear/velocity"]
     for k in (0, 1, 2):
-        r, rd = ref.extrapolate(p, v, [0.5, 1.25, 2.0], n_iter=k, vel_timestep=0.5, return_displacement=True)
+        r, rd = semilag_pins["shear/out_K%d" % k], semilag_pins["shear/disp_K%d" % k]
         for mod, kw in ((osl, dict(backend="numpy")), (ocl, {})):
             a, ad = mod.extrapolate(p, v, [0.5, 1.25, 2.0], n_iter=k, vel_timestep=0.5,
                                     return_displacement=True, **kw)
@@ -212,19 +213,12 @@ def test_boundary_modes_pinned_against_scipy(mode, order):
             np.testing.assert_allclose(got, want, rtol=1e-12, atol=1e-12, equal_nan=True)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
 @pytest.mark.parametrize("mode", BOUNDARY_MODES[1:])
-def test_oracle_boundary_modes_match_live_reference(mode):
-    ref = ref_loader.load("pysteps.extrapolation.semilagrangian")
-    rng = np.random.default_rng(23)
-    m, n = 40, 56
-    p = rng.gamma(1.0, 2.0, (m, n)).astype(np.float32)
-    p[rng.uniform(size=(m, n)) < 0.03] = np.nan
-    y, x = np.mgrid[0:m, 0:n]
-    v = np.stack([3 + 0.08 * (y - m / 2), -2 + 0.06 * (x - n / 2)]).astype(np.float32)
+def test_oracle_boundary_modes_match_live_reference(semilag_pins, mode):
+    """oracle.semilag against the reference's outputs for a field with NaN under each boundary mode (tools/make_golden.py)."""
+    p, v = semilag_pins["modes/precip"], semilag_pins["modes/velocity"]
     for order in (0, 1):
-        r = ref.extrapolate(p, v, [2.0, 9.0, 31.0], interp_order=order, map_coordinates_mode=mode, outval=-3.0,
-                            allow_nonfinite_values=True)
+        r = semilag_pins["modes/%s_o%d" % (mode, order)]
         a = osl.extrapolate(p, v, [2.0, 9.0, 31.0], interp_order=order, map_coordinates_mode=mode, outval=-3.0,
                             allow_nonfinite_values=True)
         assert nan_mismatch(a, r) == 0

@@ -5,7 +5,6 @@ import pytest
 from pysteps_amd import register
 from pysteps_amd.extrapolation.semilagrangian import extrapolate
 from pysteps_amd.motion.lucaskanade import dense_lucaskanade
-from tools import ref_loader
 
 
 def test_register_into_plain_dicts():
@@ -21,10 +20,9 @@ def test_register_into_plain_dicts():
     assert extrap["semilagrangian"] is extrapolate
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
-def test_reference_get_method_serves_the_hip_extrapolator():
+def test_reference_get_method_serves_the_hip_extrapolator(ref_pysteps):
     """The real pysteps.extrapolation.interface.get_method returns our callable by name."""
-    iface = ref_loader.load("pysteps.extrapolation.interface")
+    iface = ref_pysteps.extrapolation.interface
     saved = dict(iface._extrapolation_methods)
     try:
         register.register_into(None, iface._extrapolation_methods)

@@ -13,7 +13,6 @@ import pytest
 from conftest import GOLDEN
 from oracle import sparse as osp
 from pysteps_amd.utils import cleansing
-from tools import ref_loader
 
 
 @pytest.fixture(scope="module")
@@ -102,32 +101,24 @@ def test_outliers_errors():
         cleansing.detect_outliers(np.ones(5), 1, np.ones((4, 2)), 2)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
 def test_live_reference_cleansing():
-    cl = ref_loader.load("pysteps.utils.cleansing")
-    rng = np.random.default_rng(8)
+    """The reference's outputs for 2 .. 700 vectors with a planted outlier (tests/golden/cleansing_reference.npz)."""
+    z = np.load(os.path.join(GOLDEN, "cleansing_reference.npz"), allow_pickle=False)
     for L in (2, 5, 31, 32, 700):
-        xy = np.column_stack([rng.integers(0, 300, L), rng.integers(0, 200, L)]).astype(float)
-        uv = rng.normal(0, 1, (L, 2)) + [3, -2]
-        uv[rng.integers(0, L)] += 9
-        want = cl.detect_outliers(uv, 3, xy, 30)
-        assert np.array_equal(cleansing.detect_outliers(uv, 3, xy, 30), want)
+        c = "L%d/" % L
+        xy, uv = z[c + "xy"], z[c + "uv"]
+        assert np.array_equal(cleansing.detect_outliers(uv, 3, xy, 30), z[c + "outliers_local"])
         if L > 2:  # the global test (k=None), both the product's host mirror and the oracle
-            from oracle import sparse as osp
-
-            want_g = cl.detect_outliers(uv, 2.5, xy, None)
+            want_g = z[c + "outliers_global"]
             assert np.array_equal(cleansing.detect_outliers(uv, 2.5, xy, None), want_g)
             assert np.array_equal(osp.detect_outliers(uv, 2.5, xy, None), want_g)
-            assert np.array_equal(osp.detect_outliers(uv[:, 0], 2.5, None, None),
-                                  cl.detect_outliers(uv[:, 0], 2.5))
-        wc, wv = cl.decluster(xy, uv, 20, 1)
+            assert np.array_equal(osp.detect_outliers(uv[:, 0], 2.5, None, None), z[c + "outliers_global_1d"])
         gc, gv = cleansing.decluster(xy, uv, 20, 1)
-        np.testing.assert_allclose(gc, wc, atol=1e-12)
-        np.testing.assert_allclose(gv, wv, atol=1e-12)
-        wc, wv = cl.decluster(xy, uv, [20, 35], 2)
+        np.testing.assert_allclose(gc, z[c + "decluster_xy"], atol=1e-12)
+        np.testing.assert_allclose(gv, z[c + "decluster_uv"], atol=1e-12)
         gc, gv = cleansing.decluster(xy, uv, [20, 35], 2)
-        np.testing.assert_allclose(gc, wc, atol=1e-12)
-        np.testing.assert_allclose(gv, wv, atol=1e-12)
+        np.testing.assert_allclose(gc, z[c + "decluster2_xy"], atol=1e-12)
+        np.testing.assert_allclose(gv, z[c + "decluster2_uv"], atol=1e-12)
 
 
 def test_decluster_native_orderings():

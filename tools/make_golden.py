@@ -210,6 +210,60 @@ def make_semilag_xy():
     print("semilag xy_coords:", len(semilag_xy_cases()) + 1, "cases")
 
 
+def make_semilag_oracle_pins():
+    """The two reference comparisons of tests/test_oracle_semilag.py: a 50 x 70 gamma field under a sheared motion
+    at n_iter 0 / 1 / 2 with vel_timestep 0.5, and a 40 x 56 one with 3 % NaN under the six boundary modes other than
+    "constant" at interp_order 0 / 1."""
+    ref = ref_loader.load("pysteps.extrapolation.semilagrangian")
+    blob = {}
+    rng = np.random.default_rng(11)
+    m, n = 50, 70
+    p = rng.gamma(1.0, 2.0, (m, n)).astype(np.float32)
+    y, x = np.mgrid[0:m, 0:n]
+    v = np.stack([3 + 0.08 * (y - m / 2), -2 + 0.06 * (x - n / 2)]).astype(np.float32)
+    blob["shear/precip"], blob["shear/velocity"] = p, v
+    for k in (0, 1, 2):
+        blob["shear/out_K%d" % k], blob["shear/disp_K%d" % k] = ref.extrapolate(
+            p, v, [0.5, 1.25, 2.0], n_iter=k, vel_timestep=0.5, return_displacement=True)
+    rng = np.random.default_rng(23)
+    m, n = 40, 56
+    p = rng.gamma(1.0, 2.0, (m, n)).astype(np.float32)
+    p[rng.uniform(size=(m, n)) < 0.03] = np.nan
+    y, x = np.mgrid[0:m, 0:n]
+    v = np.stack([3 + 0.08 * (y - m / 2), -2 + 0.06 * (x - n / 2)]).astype(np.float32)
+    blob["modes/precip"], blob["modes/velocity"] = p, v
+    for mode in ("nearest", "reflect", "mirror", "wrap", "grid-constant", "grid-wrap"):
+        for order in (0, 1):
+            blob["modes/%s_o%d" % (mode, order)] = ref.extrapolate(
+                p, v, [2.0, 9.0, 31.0], interp_order=order, map_coordinates_mode=mode, outval=-3.0,
+                allow_nonfinite_values=True)
+    np.savez_compressed(os.path.join(OUT, "semilag_oracle_pins.npz"), **blob)
+    print("semilag oracle pins: 3 + 12 calls")
+
+
+def make_cleansing():
+    """tests/test_sparse_cpu.py's comparison with the reference's detect_outliers / decluster: 2 .. 700 vectors with
+    one planted outlier each; local (k=3, 30 px) and global (k=None) outlier tests, 2-d and 1-d, and declustering at
+    one and at two scales."""
+    cl = ref_loader.load("pysteps.utils.cleansing")
+    blob = {}
+    rng = np.random.default_rng(8)
+    for L in (2, 5, 31, 32, 700):
+        xy = np.column_stack([rng.integers(0, 300, L), rng.integers(0, 200, L)]).astype(float)
+        uv = rng.normal(0, 1, (L, 2)) + [3, -2]
+        uv[rng.integers(0, L)] += 9
+        c = "L%d/" % L
+        blob[c + "xy"], blob[c + "uv"] = xy, uv
+        blob[c + "outliers_local"] = cl.detect_outliers(uv, 3, xy, 30)
+        if L > 2:
+            blob[c + "outliers_global"] = cl.detect_outliers(uv, 2.5, xy, None)
+            blob[c + "outliers_global_1d"] = cl.detect_outliers(uv[:, 0], 2.5)
+        blob[c + "decluster_xy"], blob[c + "decluster_uv"] = cl.decluster(xy, uv, 20, 1)
+        blob[c + "decluster2_xy"], blob[c + "decluster2_uv"] = cl.decluster(xy, uv, [20, 35], 2)
+    np.savez_compressed(os.path.join(OUT, "cleansing_reference.npz"), **blob)
+    print("cleansing: 5 cases")
+
+
 def sparse_vectors(L, m, n, seed, outliers=True):
     """LK-like sparse vectors: integer feature positions, smooth motion + noise (+ planted outliers)."""
     rng = np.random.default_rng(seed)
@@ -284,7 +338,8 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     only = sys.argv[1:]
     for name, fn in (("semilag", make_semilag), ("semilag_order3_modes", make_semilag_order3_modes),
-                     ("semilag_xy", make_semilag_xy), ("semilag_spline_orders", make_semilag_spline_orders), ("sparse", make_sparse), ("probmatch", make_probmatch)):
+                     ("semilag_xy", make_semilag_xy), ("semilag_spline_orders", make_semilag_spline_orders), ("sparse", make_sparse), ("probmatch", make_probmatch),
+                     ("semilag_oracle_pins", make_semilag_oracle_pins), ("cleansing", make_cleansing)):
         if not only or name in only:
             fn()
 
