@@ -51,8 +51,9 @@ def hermitian_weights(n):
     return w
 
 
-def update_spectral(white, noise_filter, weights, spectra, phi, noise_std, mu, sigma):
-    """spectra: (L, p, m, n/2+1) = rfft2 of the level fields, oldest first.  Returns (new spectra (L, m, n/2+1), field)."""
+def update_spectral(white, noise_filter, weights, spectra, phi, noise_std, mu, sigma, spectrum=False):
+    """spectra: (L, p, m, n/2+1) = rfft2 of the level fields, oldest first.  Returns (new spectra (L, m, n/2+1), field);
+    spectrum=True: the recomposed half spectrum in place of the field (what the inverse transform is applied to)."""
     m, n = white.shape
     y = np.fft.rfft2(white) * noise_filter
     y[0, 0] = 0.0  # the standardised noise field has no mean
@@ -70,7 +71,7 @@ def update_spectral(white, noise_filter, weights, spectra, phi, noise_std, mu, s
         new.append(x_new)
         total = total + sigma[k] * x_new
     total[0, 0] += np.sum(mu) * m * n
-    return np.stack(new), np.fft.irfft2(total, s=(m, n))
+    return np.stack(new), (total if spectrum else np.fft.irfft2(total, s=(m, n)))
 
 
 def spectral_std(x, shape):
@@ -81,7 +82,8 @@ def spectral_std(x, shape):
     return np.sqrt(res / (m * n) ** 2)
 
 
-def update_reference_spectral_domain(randstate, shape, noise_filter, weights, compact_levels, phi, noise_std, mu, sigma):
+def update_reference_spectral_domain(randstate, shape, noise_filter, weights, compact_levels, phi, noise_std, mu, sigma,
+                                     spectrum=False):
     """One member update of ``nowcasts.steps(domain="spectral")``, operation for operation:
     pysteps/noise/fftgenerators.py:407-437 (unit phasors from ``randstate.uniform``, column 0 mirrored, filter, DC
     removed, spectral standardisation), pysteps/cascade/decomposition.py:195-236 with spectral input and output,
@@ -90,7 +92,7 @@ def update_reference_spectral_domain(randstate, shape, noise_filter, weights, co
     compact arrays), cascade/decomposition.py:284-300 (``result[mask_k] += level_k * sigma_k + mu_k``) and the one
     inverse transform of steps.py:1188-1189.
     compact_levels: list of L arrays (p, count_k) complex, oldest first (updated in place like the reference's
-    ``np.concatenate``).  Returns the recomposed field (m, n)."""
+    ``np.concatenate``).  Returns the recomposed field (m, n); spectrum=True: its half spectrum (m, n/2+1) instead."""
     m, n = shape
     nc = n // 2 + 1
     theta = randstate.uniform(low=0.0, high=2.0 * np.pi, size=(m, nc))
@@ -120,4 +122,4 @@ def update_reference_spectral_domain(randstate, shape, noise_filter, weights, co
         x_new = x_new + phi[k, -1] * eps
         compact_levels[k] = np.concatenate([x[1:, :], x_new[np.newaxis, :]])
         result[mask] += x_new * sigma[k] + mu[k]
-    return np.fft.irfft2(result, s=shape)
+    return result if spectrum else np.fft.irfft2(result, s=shape)

@@ -226,6 +226,10 @@ CONFIGS = {
     "nomask_mean": dict(mask_method=None, probmatching_method="mean"),
     "ar1_8levels": dict(mask_method="incremental", probmatching_method="cdf", ar_order=1, n_cascade_levels=8),
     "sprog_cdf": dict(mask_method="sprog", probmatching_method="cdf"),  # deterministic AR model + percentile mask per step
+    # an odd width in the default (spectral) domain: the last half-spectrum column is no Nyquist column and counts twice in
+    # the level variances; "mean" keeps the scale of the field, which a CDF matching would replace
+    "odd_width_mean": dict(mask_method="incremental", probmatching_method="mean", shape=(151, 189)),
+    "raw_recomposed": dict(mask_method=None, probmatching_method=None),  # the recomposed field itself, nothing after it
     # the reference's own spectral domain (steps.py:122-126): compact spectral state, phases from RandomState.uniform
     "refspectral_incremental_cdf": dict(mask_method="incremental", probmatching_method="cdf", domain="spectral"),
     "refspectral_composite_obs": dict(mask_method="obs", probmatching_method="mean", domain="spectral", shape=(150, 190)),
