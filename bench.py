@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - advection hot path (dense LK + semi-Lagrangian) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is
 already resident in HBM: motion estimate from the input frames (dense
@@ -16,6 +16,11 @@ own perturbed members and there is no data-path collective afterwards (weak
 scaling; an RCCL failure makes the run exit non-zero).
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the fields).
+
+A plain N = 1 run does what its headline needs and no more: inputs, warm-up, the timed steps, --dump-outputs and the
+line (headline, the two legs of the step, the rooflines from the timed steps' events and the committed counter files).
+--full adds the legs that run work of their own after the timed steps (NumPy host path, spectral leg, config-4 members,
+STEPS member loop, CPU baselines; each still switched off by its --no-* flag) and, with N > 1, the advection-only figure.
 """
 
 import argparse
@@ -73,6 +78,9 @@ def parse_args():
     ap.add_argument("--leadtimes", type=int, default=24)
     ap.add_argument("--n-iter", type=int, default=1)
     ap.add_argument("--frames", type=int, default=2, help="LK input frames")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (host path, spectral, members, STEPS loop, CPU baselines; "
+                         "N > 1: the advection-only figure); each of those legs keeps its --no-* switch")
     ap.add_argument("--no-lk", action="store_true", help="time the extrapolator only (true velocity)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-path", action="store_true", help="skip the NumPy-in / NumPy-out leg")
@@ -917,11 +925,12 @@ def main():
     line["roofline"] = semilag_roofline(m, n, T, K, sl_ms, alg_bytes)
     if have_lk:
         line["roofline_lk"] = roofline_lk(frames_d, m, n, args.frames - 1)
-    if not args.no_host_path:
+    # the legs below run work of their own after the timed steps: --full only
+    if args.full and not args.no_host_path:
         line["config"].update(host_path(frames_d, vel_d, T, K))
-    if not args.no_spectral:
+    if args.full and not args.no_spectral:
         line["config"]["spectral"] = spectral_leg(m, n)
-    if not args.no_members_leg:
+    if args.full and not args.no_members_leg:
         # what ONE GPU of the N > 1 runs does (config 4: members_per_gpu members, T single-step
         # stateful calls): the single-GPU figure the multi-GPU values are to be compared with
         mstep = members_workload(precip_d, vel_d, args.members_per_gpu, 0, args.members_per_gpu, T, K)
@@ -932,7 +941,7 @@ def main():
             "value": args.members_per_gpu * m * n * T / (el / 3) / 1e6,
             "note": "same per-GPU workload as the --gpus N > 1 runs (weak scaling reference)",
         }
-    if not args.no_steps_loop:
+    if args.full and not args.no_steps_loop:
         try:
             loop_T = min(T, 6)
             sl, e2e = steps_loop_leg(precip_d, vel_d, args.members_per_gpu, loop_T, K, dist,
@@ -947,7 +956,7 @@ def main():
     line["advection_value"] = line["config"].get("config4_one_gpu", {}).get("value")
     line["member_loop_value"] = line["config"].get("steps_loop", {}).get("value")
     line["config"]["workload"] += "; `value` = lk_semilag_value"
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(frames_d, vel_d, K, args.cpu_sample_steps, T, have_lk)
     print(json.dumps(line))
     dist.close()
@@ -1071,8 +1080,9 @@ def main_members(args, dist, dense_lk):
     # can be laid side by side: member_loop_value (update + advection), advection_value (advection alone),
     # lk_semilag_value (BASELINE config 3, N = 1 only).  `value` of this line is member_loop_value
     # (advection_value with --advection-only); its N = 1 twin is `--gpus 1 --force-members-path`
+    # (single_gpu_base stays in every line: it runs before the timed region, which starts from the state it leaves)
     advection_value = value if args.advection_only else None
-    if not args.advection_only:
+    if args.full and not args.advection_only:
         try:
             adv_step = members_workload(precip_d, vel_d, len(mine), mine.start, n_total, T, K)
             adv_el = time_steps(adv_step, dist, 2, 1)

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 rm -f gpurun_out/sl_seen.jsonl gpurun_out/update_flips_seen.jsonl
 ( time timeout 1500 python -m pytest tests -m gpu -q --timeout=400 --durations=12 ) > $OUT/pytest_gpu.txt 2>&1
 grep -E "passed|failed|error" $OUT/pytest_gpu.txt | tail -3
-timeout 600 python bench.py --steps 20 --warmup 5 2>$OUT/bench.err > $OUT/bench.json; cut -c1-420 $OUT/bench.json; echo
+timeout 600 python bench.py --steps 20 --warmup 5 --full 2>$OUT/bench.err > $OUT/bench.json; cut -c1-420 $OUT/bench.json; echo
 BENCH="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-members-leg --no-spectral --no-steps-loop --no-steps-stock"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1
 python tools/gap_analysis.py $OUT/trace > $OUT/gaps.txt 2>&1; tail -1 $OUT/gaps.txt
@@ -26,7 +26,7 @@ Q="--steps 10 --warmup 3 --no-cpu-baseline --no-host-path --no-members-leg --no-
   timeout 300 python bench.py --size 8192 --frames 2 --leadtimes 36 $Q 2>/dev/null
   timeout 200 python bench.py --size 512 --frames 2 --leadtimes 6 $Q 2>/dev/null; } > $OUT/other_shapes.jsonl
 cut -c1-200 $OUT/other_shapes.jsonl
-timeout 600 python bench.py --force-members-path --steps 3 --warmup 1 2>$OUT/members.err > $OUT/bench_members_world1.json; cut -c1-300 $OUT/bench_members_world1.json; echo
+timeout 600 python bench.py --force-members-path --steps 3 --warmup 1 --full 2>$OUT/members.err > $OUT/bench_members_world1.json; cut -c1-300 $OUT/bench_members_world1.json; echo
 timeout 600 python bench.py --force-members-path --advection-only --steps 3 --warmup 1 2>>$OUT/members.err > $OUT/bench_members_advection_world1.json
 timeout 900 python bench.py --workload config5 --steps 3 --warmup 1 2>$OUT/config5.err > $OUT/bench_config5_world1.json; cut -c1-300 $OUT/bench_config5_world1.json; echo
 timeout 900 python bench.py --workload config5 --config5-lk banded --steps 3 --warmup 1 2>>$OUT/config5.err > $OUT/bench_config5_banded_world1.json

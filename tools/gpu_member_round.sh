@@ -8,7 +8,7 @@ TAG=$1
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python bench.py --steps 2 --warmup 1 --no-lk --no-cpu-baseline --no-host-path --no-members-leg --no-spectral --no-steps-stock"
+B="python bench.py --steps 2 --warmup 1 --full --no-lk --no-cpu-baseline --no-host-path --no-members-leg --no-spectral --no-steps-stock"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/mtrace -- $B > $OUT/mtrace.log 2>&1
 grep -o '"steps_loop": {[^}]*}' $OUT/mtrace.log | head -1 > $OUT/member_steps_loop.json
 python tools/gap_update.py $OUT/mtrace > $OUT/member_update_kernels.txt 2>&1
