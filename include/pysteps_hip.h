@@ -295,6 +295,47 @@ int psh_blob_peaks_dev(const double *cube_dev, int K, int m, int n, double thres
                        double *values_host, int *count_host);
 int psh_blob_gather_dev(const double *plane_dev, int m, int n, const int *yx_host, int count, double *values_host);
 
+/* ---- the ANVIL nowcast (csrc/anvil.hip) ------------------------------------------------------------------------ *
+ * pysteps/nowcasts/anvil.py: moving-window statistics, AR(1)/AR(2) parameters, the R(VIL) regression and the
+ * per-lead-time ARI(p,1) update.  All planes float64 (m, n) unless stated; every call is queued on the library
+ * stream.  Arithmetic = NumPy / SciPy operation by operation, FP contraction off.
+ *  psh_anvil_gauss_dev   scipy.ndimage.gaussian_filter(field, sigma, mode="constant") of the fields a recipe forms
+ *      from up to three input planes, into out (nf, m, n):
+ *        PSH_ANVIL_RECIPE_PLAIN  in0[, in1[, in2]] themselves (nf = number of inputs)
+ *        PSH_ANVIL_RECIPE_CORR   x = in0, y1 = in1[, y2 = in2] -> x*x, y1*y1, x*y1[, y2*y2, x*y2] (nf 3 or 5)
+ *        PSH_ANVIL_RECIPE_RVIL   vil, r, mask -> mask, vil, vil*vil, vil*r, r (nf 5)
+ *        PSH_ANVIL_RECIPE_ONES   no input: the all-ones field (nf 1)
+ *      weights_host: radius + 1 doubles, centre then distances 1 .. radius of scipy's _gaussian_kernel1d
+ *      (radius = int(4 sigma + 0.5) <= 2048); waited for before the call returns.
+ *  psh_anvil_phi_dev     one cascade level: nwin (filtered ones) and the CORR fields -> phi (ar_order + 1 planes:
+ *      phi_0 .. phi_p of _estimate_ar{1,2}_params without the zero innovation term), through
+ *      _moving_window_corrcoef and, for ar_order 2, adjust_lag2_corrcoef2; gamma_dev (ar_order planes, the
+ *      adjusted lag-2 value) may be NULL.
+ *  psh_anvil_rvil_dev    _r_vil_regression(vil, rainrate, radius) -> a, b.
+ *  psh_anvil_masks_dev   frames (K, m, n): zero-filled copies (non-finite -> 0), mask = every frame finite (uint8),
+ *      rr_mask = mask and frames[K-1] < 0.1 (uint8; NULL: not computed).
+ *  psh_anvil_diff_dev    out = newer - older, non-finite differences -> 0.
+ *  psh_anvil_update_dev  one lead time: ring (n_levels, p, m, n) with its oldest slot at `head` (p = ar_order + 1),
+ *      phi (n_levels, p, m, n); x_new = 0 + phi_0 x[-1] + .. + phi_{p-1} x[-p] replaces the oldest slot; out =
+ *      sum of the levels in sequence, NaN where mask is 0, then a*out + b (a_dev, b_dev) or 0 where rr_mask is
+ *      set (rr_mask_dev, may be NULL), then values < 0 -> 0. */
+#define PSH_ANVIL_RECIPE_PLAIN 0
+#define PSH_ANVIL_RECIPE_CORR 1
+#define PSH_ANVIL_RECIPE_RVIL 2
+#define PSH_ANVIL_RECIPE_ONES 3
+int psh_anvil_gauss_dev(const double *in0_dev, const double *in1_dev, const double *in2_dev, int recipe, int m, int n,
+                        const double *weights_host, int radius, double *out_dev);
+int psh_anvil_phi_dev(const double *nwin_dev, const double *fields_dev, int ar_order, int m, int n, double *phi_dev,
+                      double *gamma_dev);
+int psh_anvil_rvil_dev(const double *vil_dev, const double *rainrate_dev, int m, int n, const double *weights_host,
+                       int radius, double *a_dev, double *b_dev);
+int psh_anvil_masks_dev(const double *frames_dev, int K, int m, int n, double *zeroed_dev, unsigned char *mask_dev,
+                        unsigned char *rr_mask_dev);
+int psh_anvil_diff_dev(const double *older_dev, const double *newer_dev, size_t count, double *out_dev);
+int psh_anvil_update_dev(double *ring_dev, const double *phi_dev, int n_levels, int p, int head, int m, int n,
+                         const unsigned char *mask_dev, const unsigned char *rr_mask_dev, const double *a_dev,
+                         const double *b_dev, double *out_dev);
+
 /* ---- dense Lucas-Kanade: image front end ----------------------------------- *
  * The NumPy + OpenCV stages of pysteps/motion/lucaskanade.py:205-242, per frame /
  * frame pair.  OpenCV is a third-party dependency of the reference (not in its

@@ -1,1 +1,17 @@
-"""Callers of the advection operators that are thin enough to mirror."""
+"""Callers of the advection operators that are thin enough to mirror, and the nowcasts that
+run on the device; ``get_method`` mirrors pysteps/nowcasts/interface.py for the names this package serves."""
+
+from .._registry import MethodTable
+
+_table = MethodTable("nowcast")
+
+
+def get_method(name):
+    """The nowcast registered under ``name``: ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`),
+    ``"extrapolation"`` / ``"lagrangian"`` (:func:`pysteps_amd.nowcasts.extrapolation.forecast`)."""
+    if not _table.names():
+        from . import anvil, extrapolation  # noqa: PLC0415
+
+        _table.add("anvil_hip", anvil.forecast)
+        _table.add(["extrapolation", "lagrangian"], extrapolation.forecast)
+    return _table.lookup(name)

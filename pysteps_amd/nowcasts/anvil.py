@@ -1,0 +1,351 @@
+"""The ANVIL nowcast on the GPU (mirror of pysteps/nowcasts/anvil.py ``forecast``), registered as ``"anvil_hip"``.
+
+Autoregressive integrated nowcasting of VIL or rain rate: the past frames are advected to the time of the last
+one, decomposed into a cascade, and on every cascade level an ARI(p,1) model with locally estimated parameters
+(Gaussian moving windows) carries the differenced series forward; the levels are summed and, with a rain-rate
+field, converted by a localized R = a VIL + b regression.  Every stage runs on the device:
+
+* past frames: the HIP semi-Lagrangian extrapolator;
+* cascade: ``cascade.decomposition_fft`` on the device, with ``cascade.bandpass_filters.filter_gaussian``;
+* moving-window statistics: ``scipy.ndimage.gaussian_filter(mode="constant")`` restated bit for bit
+  (``psh_anvil_gauss_dev``, csrc/anvil.hip), several fields per pass; the window count ``n`` is the same for every
+  level and lag (the differenced cascades are made finite first) and is filtered once;
+* correlations, ``adjust_lag2_corrcoef2`` and the AR parameters: one element-wise kernel per level;
+* the lead times: :func:`pysteps_amd.nowcasts.utils.nowcast_main_loop` with :class:`ResidentAnvil`, the cascade
+  history a ring in HBM and one kernel launch per lead time.
+
+Options the kernels do not implement (``ar_order`` other than 1 and 2, ``ar_window_radius=None``, another
+extrapolation method, shapes the device FFT does not take) go to the reference with a warning when pysteps is
+importable and raise ``NotImplementedError`` otherwise.
+"""
+
+import ctypes
+import time
+import warnings
+
+import numpy as np
+
+from .. import _lib
+from ..cascade.bandpass_filters import filter_gaussian
+from ..cascade.decomposition import _device_nonfinite, decomposition_fft
+from ..device import DeviceArray, Event
+from ..feature.blob import _gaussian_kernel1d
+from ..utils import fft as hip_fft
+
+__all__ = ["forecast", "gaussian_filter_dev", "moving_window_phi", "r_vil_regression", "ResidentAnvil"]
+
+RECIPE_PLAIN, RECIPE_CORR, RECIPE_RVIL, RECIPE_ONES = 0, 1, 2, 3
+MAX_RADIUS = 2048  # csrc/anvil.hip kAnvilMaxRadius
+_EXTRAPOLATORS = ("semilagrangian", "semilagrangian_hip")
+# device time of the last call (ms): {"init", "loop"}, from events on the library stream (tools/anvil_quick.py)
+last_run_stats = {}
+_filters = {}  # (shape, n, filter kwargs) -> band-pass filter; its weights stay cached on the device
+
+
+def _check_inputs(vil, rainrate, velocity, timesteps, ar_order):
+    if vil.ndim != 3:
+        raise ValueError("vil.shape = %s, but a three-dimensional array expected" % str(vil.shape))
+    if rainrate is not None:
+        if rainrate.ndim != 2:
+            raise ValueError("rainrate.shape = %s, but a two-dimensional array expected" % str(rainrate.shape))
+    if vil.shape[0] != ar_order + 2:
+        raise ValueError(
+            "vil.shape[0] = %d, but vil.shape[0] = ar_order + 2 = %d required" % (vil.shape[0], ar_order + 2)
+        )
+    if velocity.ndim != 3:
+        raise ValueError("velocity.shape = %s, but a three-dimensional array expected" % str(velocity.shape))
+    if isinstance(timesteps, list) and not sorted(timesteps) == timesteps:
+        raise ValueError("timesteps is not in ascending order")
+
+
+def _half_weights(sigma):
+    """(radius, centre and distances 1 .. radius) of the kernel scipy's gaussian_filter1d correlates with."""
+    sd = float(sigma)
+    radius = int(4.0 * sd + 0.5)
+    w = _gaussian_kernel1d(sd, 0, radius)[::-1]
+    return radius, np.ascontiguousarray(w[radius::-1], dtype=np.float64)
+
+
+def _ptr(a):
+    return None if a is None else a.ptr
+
+
+def _plane(arr, k):
+    """View of plane k of a (K, m, n) float64 DeviceArray."""
+    m, n = arr.shape[-2:]
+    return DeviceArray((m, n), np.float64, ptr=arr.ptr + k * m * n * 8, owner=arr)
+
+
+def gaussian_filter_dev(inputs, sigma, recipe=RECIPE_PLAIN):
+    """``scipy.ndimage.gaussian_filter(f, sigma, mode="constant")`` of the fields ``recipe`` forms from up to three
+    (m, n) float64 DeviceArrays (``psh_anvil_gauss_dev``): a (nf, m, n) float64 DeviceArray, bit-identical with SciPy.
+    ``inputs`` may be empty with RECIPE_ONES, ``shape`` then given as ``inputs=((m, n),)``."""
+    radius, w = _half_weights(sigma)
+    if radius > MAX_RADIUS:
+        raise NotImplementedError("pysteps_amd anvil: window radius %s (kernel radius %d > %d)" % (sigma, radius, MAX_RADIUS))
+    if recipe == RECIPE_ONES:
+        (m, n), ins, nf = inputs[0], [], 1
+    else:
+        ins = list(inputs)
+        m, n = ins[0].shape
+        nf = {RECIPE_PLAIN: len(ins), RECIPE_CORR: 3 if len(ins) == 2 else 5, RECIPE_RVIL: 5}[recipe]
+    out = DeviceArray((nf, m, n), np.float64)
+    ptrs = [_ptr(a) for a in ins] + [None] * (3 - len(ins))
+    _lib.check(_lib.lib().psh_anvil_gauss_dev(ptrs[0], ptrs[1], ptrs[2], int(recipe), int(m), int(n),
+                                              w.ctypes.data_as(ctypes.c_void_p), radius, out.ptr), "psh_anvil_gauss_dev")
+    return out
+
+
+def moving_window_phi(nwin, x, lags, sigma, return_gamma=False):
+    """AR parameters of one cascade level: ``x`` = the newest differenced plane, ``lags`` = [older planes, newest
+    first] (one or two), ``nwin`` = the filtered all-ones field.  Returns the (ar_order + 1, m, n) float64
+    DeviceArray phi_0 .. phi_p (and the (ar_order, m, n) correlations, lag 2 adjusted)."""
+    ar_order = len(lags)
+    m, n = x.shape
+    fields = gaussian_filter_dev([x] + list(lags), sigma, RECIPE_CORR)
+    phi = DeviceArray((ar_order + 1, m, n), np.float64)
+    gamma = DeviceArray((ar_order, m, n), np.float64) if return_gamma else None
+    _lib.check(_lib.lib().psh_anvil_phi_dev(nwin.ptr, fields.ptr, ar_order, m, n, phi.ptr, _ptr(gamma)), "psh_anvil_phi_dev")
+    return (phi, gamma) if return_gamma else phi
+
+
+def r_vil_regression(vil, rainrate, window_radius):
+    """``_r_vil_regression`` of the reference on (m, n) float64 DeviceArrays: the coefficient planes a, b."""
+    radius, w = _half_weights(window_radius)
+    if radius > MAX_RADIUS:
+        raise NotImplementedError("pysteps_amd anvil: R(VIL) window radius %s too large" % window_radius)
+    m, n = vil.shape
+    a = DeviceArray((m, n), np.float64)
+    b = DeviceArray((m, n), np.float64)
+    _lib.check(_lib.lib().psh_anvil_rvil_dev(vil.ptr, rainrate.ptr, m, n, w.ctypes.data_as(ctypes.c_void_p), radius,
+                                             a.ptr, b.ptr), "psh_anvil_rvil_dev")
+    return a, b
+
+
+class ResidentAnvil:
+    """The reference's ``_update`` with its state in HBM: ``update()`` advances every level's ARI model by one
+    step (the cascade history a ring of ar_order + 1 planes per level) and returns the forecast field as a
+    float64 DeviceArray (1, m, n) - one kernel launch."""
+
+    def __init__(self, ring, phi, mask, rr_mask=None, r_vil=None):
+        self.ring, self.phi, self.mask, self.rr_mask = ring, phi, mask, rr_mask
+        self.a, self.b = r_vil if r_vil is not None else (None, None)
+        self.n_levels, self.p, self.m, self.n = ring.shape
+        self.head = 0  # slot of the oldest plane of every level
+
+    def update(self):
+        out = DeviceArray((1, self.m, self.n), np.float64)
+        _lib.check(_lib.lib().psh_anvil_update_dev(self.ring.ptr, self.phi.ptr, self.n_levels, self.p, self.head, self.m,
+                                                   self.n, self.mask.ptr, _ptr(self.rr_mask), _ptr(self.a), _ptr(self.b),
+                                                   out.ptr), "psh_anvil_update_dev")
+        self.head = (self.head + 1) % self.p
+        return out
+
+    def finish(self):
+        self.ring = self.phi = self.mask = self.rr_mask = self.a = self.b = None
+
+    def abort(self):
+        self.finish()
+
+
+def _update(state, params):
+    """Host form of one update (the main loop drives ``state["resident"]`` directly; see :func:`try_create`)."""
+    return state["resident"].update().to_host()[0], state
+
+
+def try_create(func, state):
+    """The resident update behind ``func`` if it is this module's update function, else None."""
+    return state.get("resident") if func is _update and isinstance(state, dict) else None
+
+
+def _reference_forecast():
+    try:
+        from pysteps.nowcasts.anvil import forecast as ref  # noqa: PLC0415
+    except Exception:
+        return None
+    return None if ref is forecast else ref
+
+
+def _unsupported(vil, velocity, rainrate, ar_order, ar_window_radius, extrap_method):
+    if ar_order not in (1, 2):
+        return "ar_order=%s (the device path implements 1 and 2)" % ar_order
+    if ar_window_radius is None:
+        return "ar_window_radius=None (global statistics)"
+    if not isinstance(extrap_method, str) or extrap_method.lower() not in _EXTRAPOLATORS:
+        return "extrap_method=%r" % (extrap_method,)
+    if not hip_fft.supported_shape(tuple(vil.shape[1:])):
+        return "shape %s (not taken by the device FFT)" % (tuple(vil.shape[1:]),)
+    if int(4.0 * float(ar_window_radius) + 0.5) > MAX_RADIUS:
+        return "ar_window_radius=%s (kernel radius above %d)" % (ar_window_radius, MAX_RADIUS)
+    return None
+
+
+def _bandpass(shape, n_levels, filter_kwargs):
+    key = (tuple(shape), int(n_levels), tuple(sorted(filter_kwargs.items())))
+    bp = _filters.get(key)
+    if bp is None:
+        bp = filter_gaussian(tuple(shape), n_levels, **filter_kwargs)
+        if len(_filters) >= 4:
+            _filters.pop(next(iter(_filters)))
+        _filters[key] = bp
+    return bp
+
+
+def _as_f64_device(a):
+    if isinstance(a, DeviceArray):
+        if a.dtype == np.float64:
+            return a
+        out = DeviceArray(a.shape, np.float64)
+        _lib.check(_lib.lib().psh_convert_dev(a.ptr, out.ptr, a.size, 1), "psh_convert_dev")
+        return out
+    return DeviceArray.from_host(np.ascontiguousarray(a, dtype=np.float64))
+
+
+def forecast(vil, velocity, timesteps, rainrate=None, n_cascade_levels=6, extrap_method="semilagrangian", ar_order=2,
+             ar_window_radius=50, r_vil_window_radius=3, fft_method="numpy", apply_rainrate_mask=True, num_workers=1,
+             extrap_kwargs=None, filter_kwargs=None, measure_time=False):
+    """Generate a nowcast with the ANVIL method (reference: pysteps/nowcasts/anvil.py; parameters, printed summary
+    and return value as documented there): an array ``(num_timesteps, m, n)``, or ``(array, init time, main loop
+    time)`` with ``measure_time``.  ``fft_method`` and ``num_workers`` are accepted; the transforms run on the
+    device.  DeviceArray inputs give a DeviceArray output."""
+    _check_inputs(vil, rainrate, velocity, timesteps, ar_order)
+    resident_in = isinstance(vil, DeviceArray)
+    why = _unsupported(vil, velocity, rainrate, ar_order, ar_window_radius, extrap_method)
+    if why is None and int(4.0 * float(r_vil_window_radius) + 0.5) > MAX_RADIUS and rainrate is not None:
+        why = "r_vil_window_radius=%s" % r_vil_window_radius
+    if why is not None:
+        ref = _reference_forecast()
+        if ref is None or resident_in or isinstance(velocity, DeviceArray) or isinstance(rainrate, DeviceArray):
+            raise NotImplementedError("pysteps_amd anvil: %s is not implemented on the device and pysteps is not "
+                                      "importable for the reference's forecast" % why)
+        warnings.warn("pysteps_amd anvil: %s - running the reference's forecast" % why, stacklevel=2)
+        return ref(vil, velocity, timesteps, rainrate=rainrate, n_cascade_levels=n_cascade_levels,
+                   extrap_method=extrap_method, ar_order=ar_order, ar_window_radius=ar_window_radius,
+                   r_vil_window_radius=r_vil_window_radius, fft_method=fft_method,
+                   apply_rainrate_mask=apply_rainrate_mask, num_workers=num_workers, extrap_kwargs=extrap_kwargs,
+                   filter_kwargs=filter_kwargs, measure_time=measure_time)
+
+    extrap_kwargs = dict() if extrap_kwargs is None else extrap_kwargs.copy()
+    if filter_kwargs is None:
+        filter_kwargs = dict()
+
+    print("Computing ANVIL nowcast")
+    print("-----------------------")
+    print("")
+    print("Inputs")
+    print("------")
+    print(f"input dimensions: {vil.shape[1]}x{vil.shape[2]}")
+    print("")
+    print("Methods")
+    print("-------")
+    print(f"extrapolation:   {extrap_method}")
+    print(f"FFT:             {fft_method}")
+    print("")
+    print("Parameters")
+    print("----------")
+    if isinstance(timesteps, int):
+        print(f"number of time steps:        {timesteps}")
+    else:
+        print(f"time steps:                  {timesteps}")
+    print(f"parallel threads:            {num_workers}")
+    print(f"number of cascade levels:    {n_cascade_levels}")
+    print(f"order of the ARI(p,1) model: {ar_order}")
+    if type(ar_window_radius) == int:  # noqa: E721 - the reference's test
+        print(f"ARI(p,1) window radius:      {ar_window_radius}")
+    else:
+        print("ARI(p,1) window radius:      none")
+    print(f"R(VIL) window radius:        {r_vil_window_radius}")
+
+    if measure_time:
+        starttime_init = time.time()
+    lib = _lib.lib()
+    ev_start = Event().record()
+    K, m, n = (int(s) for s in vil.shape)
+    plane = m * n
+    bp_filter = _bandpass((m, n), n_cascade_levels, filter_kwargs)  # the reference's checks (n > 2) come first
+
+    frames = _as_f64_device(vil)
+    allow_nonfinite = _device_nonfinite(frames)
+    vel32 = velocity if isinstance(velocity, DeviceArray) else DeviceArray.from_host(np.asarray(velocity), dtype=np.float32)
+    if vel32.dtype != np.float32:
+        v = DeviceArray(vel32.shape, np.float32)
+        _lib.check(lib.psh_convert_dev(vel32.ptr, v.ptr, vel32.size, 0), "psh_convert_dev")
+        vel32 = v
+
+    r_vil = None
+    if rainrate is not None:
+        r_vil = r_vil_regression(_plane(frames, K - 1), _as_f64_device(rainrate), r_vil_window_radius)
+
+    # the past frames advected to the time of the last one (the reference's worker loop); the last stays as it is
+    from ..extrapolation.semilagrangian import extrapolate  # noqa: PLC0415
+
+    advected = DeviceArray((K, m, n), np.float64)
+    kw = dict(extrap_kwargs, allow_nonfinite_values=allow_nonfinite)
+    kw.pop("return_displacement", None)
+    f32 = DeviceArray((m, n), np.float32)
+    for i in range(K - 1):
+        _lib.check(lib.psh_convert_dev(frames.ptr + i * plane * 8, f32.ptr, plane, 0), "psh_convert_dev")
+        moved = extrapolate(f32, vel32, K - 1 - i, **kw)
+        last = moved.ptr + (moved.shape[0] - 1) * plane * 4
+        _lib.check(lib.psh_convert_dev(last, advected.ptr + i * plane * 8, plane, 1), "psh_convert_dev")
+    _lib.check(lib.psh_memcpy_d2d(advected.ptr + (K - 1) * plane * 8, frames.ptr + (K - 1) * plane * 8, plane * 8), "d2d")
+
+    # finite mask of the advected frames, zero-filled copies to decompose, the rain-rate mask
+    zeroed = DeviceArray((K, m, n), np.float64)
+    mask = DeviceArray((m, n), np.uint8)
+    rr_mask = DeviceArray((m, n), np.uint8) if (rainrate is None and apply_rainrate_mask) else None
+    _lib.check(lib.psh_anvil_masks_dev(advected.ptr, K, m, n, zeroed.ptr, mask.ptr, _ptr(rr_mask)), "psh_anvil_masks_dev")
+    del advected
+
+    cascades = [decomposition_fft(_plane(zeroed, k), bp_filter, compute_stats=False)["cascade_levels"] for k in range(K)]
+    del zeroed
+
+    # per level: differenced cascades -> filtered moments -> phi; the window count is the same for every level
+    p = ar_order + 1
+    nwin = gaussian_filter_dev(((m, n),), ar_window_radius, RECIPE_ONES)
+    phi = DeviceArray((n_cascade_levels, p, m, n), np.float64)
+    ring = DeviceArray((n_cascade_levels, p, m, n), np.float64)
+    diffs = DeviceArray((K - 1, m, n), np.float64)
+    for lev in range(n_cascade_levels):
+        for k in range(K - 1):
+            _lib.check(lib.psh_anvil_diff_dev(cascades[k].ptr + lev * plane * 8, cascades[k + 1].ptr + lev * plane * 8,
+                                              plane, diffs.ptr + k * plane * 8), "psh_anvil_diff_dev")
+        x = _plane(diffs, K - 2)
+        lags = [_plane(diffs, K - 3 - j) for j in range(ar_order)]
+        level_phi = moving_window_phi(nwin, x, lags, ar_window_radius)
+        _lib.check(lib.psh_memcpy_d2d(phi.ptr + lev * p * plane * 8, level_phi.ptr, p * plane * 8), "d2d")
+        for s in range(p):  # the ring starts with the last p cascades, oldest in slot 0
+            _lib.check(lib.psh_memcpy_d2d(ring.ptr + (lev * p + s) * plane * 8,
+                                          cascades[K - p + s].ptr + lev * plane * 8, plane * 8), "d2d")
+    del cascades, diffs, nwin
+    ev_init = Event().record()
+
+    if measure_time:
+        _lib.check(lib.psh_sync(), "psh_sync")
+        init_time = time.time() - starttime_init
+
+    print("Starting nowcast computation.")
+
+    extrap_kwargs["return_displacement"] = True
+    extrap_kwargs["allow_nonfinite_values"] = allow_nonfinite
+    state = {"resident": ResidentAnvil(ring, phi, mask, rr_mask, r_vil)}
+    params = {"apply_rainrate_mask": apply_rainrate_mask, "n_cascade_levels": n_cascade_levels, "rainrate": rainrate}
+    last_frame = frames.to_host()[K - 1] if resident_in else np.asarray(vil[-1, :])
+    motion = velocity.to_host() if isinstance(velocity, DeviceArray) else velocity
+
+    from .utils import nowcast_main_loop  # noqa: PLC0415
+
+    result = nowcast_main_loop(last_frame, motion, state, timesteps, extrap_method, _update, extrap_kwargs=extrap_kwargs,
+                               params=params, measure_time=measure_time)
+    if measure_time:
+        result, mainloop_time = result
+    ev_end = Event().record()
+    _lib.check(lib.psh_sync(), "psh_sync")
+    out = np.stack(result)
+    last_run_stats.clear()
+    last_run_stats.update(init=ev_start.elapsed_ms(ev_init), loop=ev_init.elapsed_ms(ev_end))
+    if resident_in:
+        out = DeviceArray.from_host(out)
+    if measure_time:
+        return out, init_time, mainloop_time
+    return out

@@ -310,7 +310,16 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
     started = time.time()  # like the reference (utils.py:347): set-up of the loop is part of its time
     plan = _time_bins(timesteps)
     extrap_kwargs = {} if extrap_kwargs is None else dict(extrap_kwargs)
+    # the ANVIL update of nowcasts/anvil.py with its cascade state in HBM: a single field per step, advected by the
+    # HIP extrapolator whatever pysteps' own table maps the name to
+    anvil = None
+    if not ensemble:
+        from .anvil import try_create as anvil_resident  # noqa: PLC0415
+
+        anvil = anvil_resident(func, state)
     try:
+        if anvil is not None:
+            raise ImportError
         from pysteps import extrapolation as ref_extrapolation  # noqa: PLC0415
 
         extrapolator = ref_extrapolation.get_method(extrap_method)
@@ -351,6 +360,10 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
                 timeline.mark("upload")
                 if isinstance(engine, _BatchedLoop):
                     engine.timeline = timeline
+
+    if anvil is not None:
+        resident, timeline = anvil, _Timeline()
+        timeline.mark("upload")
 
     prev = np.stack([precip] * n_members) if ensemble else precip[np.newaxis, :]
     outputs = [[] for _ in range(prev.shape[0])] if return_output else None
@@ -430,7 +443,7 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
     result = None
     if block is not None:
         _lib.check(_lib.lib().psh_sync(), "psh_sync")
-        result = block
+        result = block if ensemble else block[0]
     elif return_output:
         result = np.stack([np.stack(o) for o in outputs])
         if not ensemble:

@@ -224,6 +224,17 @@ def unpatch_dilated_mask():
         del ref_mod._reference_compute_dilated_mask
 
 
+def register_nowcasts():
+    """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) to pysteps' nowcast table
+    (pysteps/nowcasts/interface.py ``_nowcast_methods``); the stock ``"anvil"`` stays the reference's."""
+    import pysteps.nowcasts.interface as now_if  # noqa: PLC0415
+
+    from .nowcasts.anvil import forecast  # noqa: PLC0415
+
+    now_if._nowcast_methods["anvil_hip"] = forecast
+    return ["nowcast:anvil_hip"]
+
+
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
              dilated_mask=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
@@ -246,6 +257,10 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += register_features(override=override)
     except ImportError:
         pass  # pysteps.feature needs none of its optional dependencies at import time; a stripped-down install may lack it
+    try:
+        added += register_nowcasts()
+    except ImportError:
+        pass  # pysteps.nowcasts imports every nowcast module; a stripped-down install may lack one's dependencies
     if fft:
         added += register_fft()
         added += register_spectral()
