@@ -128,7 +128,7 @@ int psh_field_stats_dev(const float *in_dev, size_t n, double *min_out, double *
  *  outval      value for pixels advected from outside the domain (may be NaN)
  *  disp        (2,m,n) float64 or NULL; resume = 1: it holds displacement_prev; resume = 2 (PSH_SL_RESUME_BASE): it
  *              holds the base positions of a custom xy_coords grid relative to the integer grid (see PSH_SL_BASE_IN_DISP)
- *              on entry (:203-207); if non-NULL it receives the final displacement
+ *              on entry (:203-207); if non-NULL it receives the final displacement.  Any other resume is PSH_EINVAL
  *  out         (T,m,n) float32, required iff precip != NULL
  */
 #define PSH_MODE_CONSTANT 0      /* scipy.ndimage mode names: "constant" (the default) */
@@ -215,7 +215,9 @@ int psh_host_free(void *host_ptr);
  *  precip (B,m,n) f32 or NULL; velocity (2,m,n); vhat = V_par (2,m,n) from
  *  psh_velocity_unit_dev, or NULL for "no perturbation"; pert_par/pert_perp: B doubles in HOST
  *  memory; disp (B,2,m,n) f64 in/out, stays resident between calls (resume=0: start from zero
- *  displacement); out (B,T,m,n) f32. */
+ *  displacement, resume=1: disp holds displacement_prev); out (B,T,m,n) f32.  The member entry points
+ *  take no base positions: any resume other than 0 or 1 (PSH_SL_RESUME_BASE included) is PSH_EINVAL.
+ *  psh_velocity_unit_dev: V / |V| (zero where |V| <= 1e-12 or NaN), |V| formed without overflow. */
 int psh_velocity_unit_dev(const float *velocity_dev, int m, int n, float *vhat_dev);
 int psh_semilag_members_dev(const float *precip_dev, const float *velocity_dev,
                             const float *vhat_dev, const double *pert_par_host,

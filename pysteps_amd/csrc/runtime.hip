@@ -523,6 +523,8 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
   if (precip_dev && !out_dev) return fail(PSH_EINVAL, "semilag: precip given but out is NULL");
   if (!precip_dev && !disp_dev)
     return fail(PSH_EINVAL, "semilag: precip is NULL but no displacement buffer was given");
+  if (resume < 0 || resume > PSH_SL_RESUME_BASE)
+    return fail(PSH_EINVAL, "semilag: resume %d is not 0, 1 or %d (PSH_SL_RESUME_BASE)", resume, PSH_SL_RESUME_BASE);
   if (resume && !disp_dev) return fail(PSH_EINVAL, "semilag: resume without displacement");
   psh::Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);

@@ -18,6 +18,7 @@
 // through buffer descriptors; roofline = HBM, 48 B/pixel/step algorithmic at
 // n_iter=1 (D read+write 32, precip in/out 8, velocity passes amortised by L2).
 #include <algorithm>
+#include <cfloat>
 
 #include "common.h"
 
@@ -224,8 +225,8 @@ __global__ __launch_bounds__(256) void semilag_members(
   if (resume) {
     if (COMPACT) {
       const uint4 r = *record;
-      px += static_cast<int>(r.x);
-      py += static_cast<int>(r.y);
+      px = sat_add(px, static_cast<int>(r.x));
+      py = sat_add(py, static_cast<int>(r.y));
       fx = __uint_as_float(r.z);
       fy = __uint_as_float(r.w);
     } else {
@@ -288,8 +289,9 @@ __global__ __launch_bounds__(256) void semilag_members(
   }
   if (live) {
     if (COMPACT) {
-      *record = make_uint4(static_cast<unsigned>(px - xc), static_cast<unsigned>(py - yc), __float_as_uint(fx),
-                           __float_as_uint(fy));
+      // saturating: a trajectory parked near INT_MIN minus its pixel index would wrap to the positive side
+      *record = make_uint4(static_cast<unsigned>(sat_sub(px, xc)), static_cast<unsigned>(sat_sub(py, yc)),
+                           __float_as_uint(fx), __float_as_uint(fy));
     } else {
       dplane[pix] = static_cast<double>(px) - static_cast<double>(xc) + static_cast<double>(fx);
       dplane[plane + pix] = static_cast<double>(py) - static_cast<double>(yc) + static_cast<double>(fy);
@@ -436,12 +438,12 @@ __global__ __launch_bounds__(256) void semilag_members_pair(
   }
   if (resume) {
     const uint4 r0 = *record[0], r1 = *record[1];
-    tr[0].px += static_cast<int>(r0.x);
-    tr[0].py += static_cast<int>(r0.y);
+    tr[0].px = sat_add(tr[0].px, static_cast<int>(r0.x));
+    tr[0].py = sat_add(tr[0].py, static_cast<int>(r0.y));
     tr[0].fx = __uint_as_float(r0.z);
     tr[0].fy = __uint_as_float(r0.w);
-    tr[1].px += static_cast<int>(r1.x);
-    tr[1].py += static_cast<int>(r1.y);
+    tr[1].px = sat_add(tr[1].px, static_cast<int>(r1.x));
+    tr[1].py = sat_add(tr[1].py, static_cast<int>(r1.y));
     tr[1].fx = __uint_as_float(r1.z);
     tr[1].fy = __uint_as_float(r1.w);
   }
@@ -532,10 +534,10 @@ __global__ __launch_bounds__(256) void semilag_members_pair(
     }
   }
   if (live) {
-    *record[0] = make_uint4(static_cast<unsigned>(tr[0].px - xc), static_cast<unsigned>(tr[0].py - yc), __float_as_uint(tr[0].fx),
-                            __float_as_uint(tr[0].fy));
+    *record[0] = make_uint4(static_cast<unsigned>(sat_sub(tr[0].px, xc)), static_cast<unsigned>(sat_sub(tr[0].py, yc)),
+                            __float_as_uint(tr[0].fx), __float_as_uint(tr[0].fy));
     if (second)
-      *record[1] = make_uint4(static_cast<unsigned>(tr[1].px - xc), static_cast<unsigned>(tr[1].py - yc),
+      *record[1] = make_uint4(static_cast<unsigned>(sat_sub(tr[1].px, xc)), static_cast<unsigned>(sat_sub(tr[1].py, yc)),
                               __float_as_uint(tr[1].fx), __float_as_uint(tr[1].fy));
   }
 }
@@ -571,8 +573,16 @@ __global__ __launch_bounds__(256) void velocity_unit(const float *__restrict__ v
                                                      float *__restrict__ vhat) {
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < plane; i += stride) {
-    const float u = vel[i], v = vel[plane + i];
-    const float nrm = sqrtf(u * u + v * v);
+    float u = vel[i], v = vel[plane + i];
+    float nrm = sqrtf(u * u + v * v);
+    if (nrm == __builtin_huge_valf() && fabsf(u) <= FLT_MAX && fabsf(v) <= FLT_MAX) {
+      // u^2 + v^2 overflowed (|V| >~ 1.8e19, a sentinel value): normalise the scaled vector, so that V_par is the
+      // unit vector of the float64 reference instead of finite / inf = 0
+      const float s = fmaxf(fabsf(u), fabsf(v));
+      u /= s;
+      v /= s;
+      nrm = sqrtf(u * u + v * v);
+    }
     const bool ok = nrm > 1e-12f;
     vhat[i] = ok ? u / nrm : 0.f;
     vhat[plane + i] = ok ? v / nrm : 0.f;
@@ -635,6 +645,9 @@ static int members_step(const float *precip_dev, const float *velocity_dev, cons
     return psh::fail(PSH_EUNSUPPORTED, "semilag_members: packed planes need m*n < 2^28 pixels");
   if (T <= 0 || T > 1024) return psh::fail(PSH_EINVAL, "semilag_members: T must be in 1..1024");
   if (n_iter < 0) return psh::fail(PSH_EINVAL, "semilag_members: n_iter must be >= 0");
+  // the kernels test `if (resume)`: base positions (PSH_SL_RESUME_BASE) would be taken as displacement_prev
+  if (resume != 0 && resume != 1)
+    return psh::fail(PSH_EINVAL, "semilag_members: resume must be 0 or 1 (got %d)", resume);
   if (interp_order != 0 && interp_order != 1)
     return psh::fail(PSH_EUNSUPPORTED, "semilag_members: interp_order %d not implemented", interp_order);
   if (!velocity_dev || !steps_host || !disp_dev)
