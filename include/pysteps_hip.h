@@ -338,6 +338,29 @@ int psh_anvil_update_dev(double *ring_dev, const double *phi_dev, int n_levels, 
                          const unsigned char *mask_dev, const unsigned char *rr_mask_dev, const double *a_dev,
                          const double *b_dev, double *out_dev);
 
+/* ---- the DARTS motion estimate (csrc/darts.hip) ---------------------------------------------------------------- *
+ * pysteps/motion/darts.py: the spectral band of the frames, the normal equations and the dense field; the small
+ * solve stays on the host.  K_y = N_y + M_y, K_x = N_x + M_x; every call is queued on the library stream.
+ *  psh_darts_nonfinite_dev  *flag_host = 1 if any of `count` values (float32 if f32, else float64) is NaN or
+ *      infinite, else 0; waits for the result.
+ *  psh_darts_band_dev   frames (T, m, n) float32 (f32) or float64 -> cube (2N_t+1, 2K_y+1, 2K_x+1) complex128:
+ *      cube[t', y', x'] = fftn(frames moved to (m, n, T))[(y' - K_y) mod m, (x' - K_x) mod n, (t' - N_t) mod T],
+ *      through rfft2 per frame (Hermitian symmetry for the bins it does not keep) and a T-point DFT along time;
+ *      T <= 64, K_y < m, K_x < n, N_t < T.
+ *  psh_darts_gram_dev   from the cube: out_host (ncol, ncol + 1) complex128, ncol = 2 (2M_y+1)(2M_x+1) <= 128:
+ *      columns 0 .. ncol-1 = M^H M, column ncol = M^H y, for M = [A | B] and y of the reference with
+ *      cy = c1 / T_y, cx = c1 / T_x.  Deterministic reduction; waits for the result.
+ *  psh_darts_rows_dev   the same M (rows, ncol) and y (rows) written out, rows = (2N_t+1)(2N_y+1)(2N_x+1).
+ *  psh_darts_synth_dev  out (2, m, n) float32 (f32) or float64 = Re(ifft2) of two spectra that are zero except at
+ *      the nb <= 64 bins (ky_host[b], kx_host[b]) (in [0, m) x [0, n)), values_host (2, nb) complex128. */
+int psh_darts_nonfinite_dev(const void *frames_dev, int f32, size_t count, int *flag_host);
+int psh_darts_band_dev(const void *frames_dev, int f32, int T, int m, int n, int ky, int kx, int nt, void *cube_dev);
+int psh_darts_gram_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx, double cy, double cx, void *out_host);
+int psh_darts_rows_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx, double cy, double cx, void *M_dev,
+                       void *y_dev);
+int psh_darts_synth_dev(const int *ky_host, const int *kx_host, const void *values_host, int nb, int m, int n, int f32,
+                        void *out_dev);
+
 /* ---- dense Lucas-Kanade: image front end ----------------------------------- *
  * The NumPy + OpenCV stages of pysteps/motion/lucaskanade.py:205-242, per frame /
  * frame pair.  OpenCV is a third-party dependency of the reference (not in its

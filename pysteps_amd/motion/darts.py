@@ -1,0 +1,310 @@
+"""The DARTS motion estimate on the GPU (mirror of pysteps/motion/darts.py ``DARTS``), registered as ``"darts_hip"``.
+
+DARTS fits the advection field's lowest (2 M_y + 1) x (2 M_x + 1) Fourier coefficients to the lowest
+(2 N_t + 1) x (2 N_y + 1) x (2 N_x + 1) coefficients of the frames' 3-d spectrum in the least-squares sense.
+The reference forms the whole spectrum with ``fftn``, fills the row matrix ``M = [A | B]`` row by row in Python and
+solves ``M x = y``.  Here (csrc/darts.hip):
+
+* the spectrum: ``rfft2`` of every frame on the device (csrc/fft.hip, one scratch spectrum), the bins the reference
+  reads gathered into a small band (wrapped as NumPy's negative indices wrap, Hermitian symmetry for the bins rfft2
+  does not keep), then a T-point DFT along time (``psh_darts_band_dev``);
+* ``M^H M`` and ``M^H y`` straight from the band, each entry of M formed as the reference forms it, with a
+  deterministic two-pass reduction (``psh_darts_gram_dev``); for ``lsq_method=1`` M and y are written out and
+  ``numpy.linalg.lstsq`` runs on the host (``psh_darts_rows_dev``);
+* the host solves the small system with the reference's ``_leastsq`` arithmetic;
+* the field: Re(ifft2) of the filled spectrum as a direct sum over its at most (2 M_y + 1)(2 M_x + 1) bins
+  (``psh_darts_synth_dev``).
+
+A DeviceArray (T, m, n) in gives a DeviceArray out (float32 for float32 frames, the form ``dense_lucaskanade``
+returns and ``semilagrangian_hip`` takes); only the small system crosses the bus.  ``fft_method`` and
+``n_threads`` are accepted and ignored.  Shapes the device FFT does not take go to the reference with a warning
+when pysteps is importable and raise ``NotImplementedError`` otherwise.
+"""
+
+import ctypes
+import time
+import warnings
+
+import numpy as np
+
+from .. import _lib
+from ..device import DeviceArray, Event, synchronize
+from ..utils import fft as hip_fft
+
+__all__ = ["DARTS", "band_cube", "gram", "row_matrix", "synthesize", "solve_leastsq", "fill_bins"]
+
+MAX_FRAMES = 64  # csrc/darts.hip kDartsMaxFrames
+MAX_COLUMNS = 128  # kDartsMaxCols: 2 (2 M_y + 1)(2 M_x + 1)
+# device time of the last call (ms): {"band", "gram", "solve", "synth", "total"} (tools/darts_quick.py)
+last_run_stats = {}
+
+
+def _check_ndim(input_images):
+    """``pysteps.decorators.check_input_frames(just_ndim=True)``"""
+    if input_images.ndim != 3:
+        raise ValueError(
+            "input_images dimension mismatch.\n"
+            f"input_images.shape: {str(input_images.shape)}\n"
+            "(t, x, y ) dimensions expected"
+        )
+
+
+def _options(kwargs):
+    return dict(
+        N_x=kwargs.get("N_x", 50),
+        N_y=kwargs.get("N_y", 50),
+        N_t=kwargs.get("N_t", 4),
+        M_x=kwargs.get("M_x", 2),
+        M_y=kwargs.get("M_y", 2),
+        output_type=kwargs.get("output_type", "spatial"),
+        lsq_method=kwargs.get("lsq_method", 2),
+        verbose=kwargs.get("verbose", True),
+    )
+
+
+def _raise_index_error(shape, o):
+    """Raise the IndexError the reference's loops raise first for these sizes (nothing if every index is valid).
+
+    A bin index k of a side s is valid for NumPy when -s <= k < s.  The reference reads k_y in [-N_y, N_y] for y and
+    k_y - kp_y in [-(N_y + M_y), N_y + M_y] for the matrix (x alike); the time index is always valid once
+    N_t < T - 1.  When one is invalid the reference's index pattern is replayed on a zero-strided stand-in of the
+    spectrum, so that the exception and its message are NumPy's own."""
+    m, n, T = shape
+    if o["N_y"] + o["M_y"] < m and o["N_x"] + o["M_x"] < n and o["N_y"] <= m and o["N_x"] <= n:
+        return
+    F = np.broadcast_to(np.zeros((), dtype=complex), (m, n, T))
+    N_x, N_y, N_t, M_x, M_y = o["N_x"], o["N_y"], o["N_t"], o["M_x"], o["M_y"]
+    rows = (2 * N_x + 1) * (2 * N_y + 1) * (2 * N_t + 1)
+    cols = (2 * M_x + 1) * (2 * M_y + 1)
+    k_t, k_y, k_x = np.unravel_index(np.arange(rows), (2 * N_t + 1, 2 * N_y + 1, 2 * N_x + 1))
+    for i in range(rows):
+        F[k_y[i] - N_y, k_x[i] - N_x, k_t[i] - N_t]
+    kp_y, kp_x = np.unravel_index(np.arange(cols), (2 * M_y + 1, 2 * M_x + 1))
+    for i in range(rows):
+        F[k_y[i] - N_y - (kp_y - M_y), k_x[i] - N_x - (kp_x - M_x), k_t[i] - N_t]
+
+
+def _unsupported(shape, o):
+    """Why the device path does not take this call (None if it does)."""
+    T, m, n = shape
+    if not hip_fft.supported_shape((m, n)):
+        return "shape %s (not taken by the device FFT)" % ((m, n),)
+    if T > MAX_FRAMES:
+        return "%d frames (the device path takes at most %d)" % (T, MAX_FRAMES)
+    if min(o["N_x"], o["N_y"], o["N_t"], o["M_x"], o["M_y"]) < 0:
+        return "a negative coefficient count"
+    if 2 * (2 * o["M_x"] + 1) * (2 * o["M_y"] + 1) > MAX_COLUMNS:
+        return "M_x=%d, M_y=%d (the device path takes at most %d unknowns)" % (o["M_x"], o["M_y"], MAX_COLUMNS)
+    return None
+
+
+def _reference_darts():
+    try:
+        from pysteps.motion.darts import DARTS as ref  # noqa: PLC0415
+    except Exception:
+        return None
+    return None if ref is DARTS else ref
+
+
+def band_cube(frames, N_y, N_x, N_t, M_y=0, M_x=0):
+    """The bins of ``fftn(moveaxis(frames, 0, -1))`` the reference reads, as a (2 N_t + 1, 2 K_y + 1, 2 K_x + 1)
+    complex128 DeviceArray (K = N + M): entry [t', y', x'] is bin ((y' - K_y) mod m, (x' - K_x) mod n,
+    (t' - N_t) mod T).  ``frames``: (T, m, n) float32 or float64 DeviceArray."""
+    T, m, n = frames.shape
+    ky, kx = N_y + M_y, N_x + M_x
+    cube = DeviceArray((2 * N_t + 1, 2 * ky + 1, 2 * kx + 1), np.complex128)
+    _lib.check(_lib.lib().psh_darts_band_dev(frames.ptr, int(frames.dtype == np.float32), T, m, n, ky, kx, N_t, cube.ptr),
+               "psh_darts_band_dev")
+    return cube
+
+
+def _coefficients(shape, o):
+    """c1 / T_y and c1 / T_x with the reference's arithmetic (darts.py: c1 = -1.0 * T_t / (T_x * T_y))."""
+    T_t, T_y, T_x = shape
+    c1 = -1.0 * T_t / (T_x * T_y)
+    return c1 / T_y, c1 / T_x
+
+
+def gram(cube, shape, o):
+    """(M^H M, M^H y) of the reference's system from the band cube: host complex128 arrays (ncol, ncol), (ncol,)."""
+    cy, cx = _coefficients(shape, o)
+    ncol = 2 * (2 * o["M_y"] + 1) * (2 * o["M_x"] + 1)
+    out = np.empty((ncol, ncol + 1), dtype=np.complex128)
+    _lib.check(_lib.lib().psh_darts_gram_dev(cube.ptr, o["N_t"], o["N_y"], o["N_x"], o["M_y"], o["M_x"], cy, cx,
+                                             out.ctypes.data_as(ctypes.c_void_p)), "psh_darts_gram_dev")
+    return np.ascontiguousarray(out[:, :ncol]), np.ascontiguousarray(out[:, ncol])
+
+
+def row_matrix(cube, shape, o):
+    """The reference's ``np.hstack([A, B])`` and ``y`` as complex128 DeviceArrays (rows, ncol) and (rows,)."""
+    cy, cx = _coefficients(shape, o)
+    rows = (2 * o["N_t"] + 1) * (2 * o["N_y"] + 1) * (2 * o["N_x"] + 1)
+    ncol = 2 * (2 * o["M_y"] + 1) * (2 * o["M_x"] + 1)
+    M = DeviceArray((rows, ncol), np.complex128)
+    y = DeviceArray((rows,), np.complex128)
+    _lib.check(_lib.lib().psh_darts_rows_dev(cube.ptr, o["N_t"], o["N_y"], o["N_x"], o["M_y"], o["M_x"], cy, cx, M.ptr,
+                                             y.ptr), "psh_darts_rows_dev")
+    return M, y
+
+
+def solve_leastsq(MM, Mhy):
+    """The reference's ``_leastsq`` on the normal equations: pseudo-inverse of MM from its SVD, singular values
+    below 0.01 s[0] dropped, times M^H y.  Returns (x, s)."""
+    U, s, V = np.linalg.svd(MM, full_matrices=False)
+    mask = s > 0.01 * s[0]
+    s_inv = 1.0 / s[mask]
+    MM_inv = np.dot(np.dot(V[: len(s_inv), :].conjugate().T, np.diag(s_inv)), U[:, : len(s_inv)].conjugate().T)
+    return np.dot(MM_inv, Mhy), s
+
+
+def fill_bins(U, V, m, n, M_y, M_x):
+    """The non-trivial bins of the reference's ``_fill(U, m, n, k_x, k_y)`` and ``_fill(V, ...)``: (ky, kx) in
+    [0, m) x [0, n) and the (2, nb) values.  Where bins coincide (sides below 2 M + 1) NumPy's own fancy assignment
+    on the (m, n) spectrum decides, as in the reference."""
+    k_x, k_y = np.meshgrid(np.arange(-M_x, M_x + 1), np.arange(-M_y, M_y + 1))
+    if 2 * M_y + 1 <= m and 2 * M_x + 1 <= n:
+        return (k_y.ravel() % m).astype(np.int32), (k_x.ravel() % n).astype(np.int32), np.stack([U.ravel(), V.ravel()])
+    pos = sorted(set(zip((k_y.ravel() % m).tolist(), (k_x.ravel() % n).tolist())))
+    ky = np.array([p[0] for p in pos], dtype=np.int32)
+    kx = np.array([p[1] for p in pos], dtype=np.int32)
+    vals = []
+    for X in (U, V):
+        X_f = np.zeros((m, n), dtype=complex)
+        X_f[k_y, k_x] = X
+        vals.append(X_f[ky, kx])
+    return ky, kx, np.stack(vals)
+
+
+def synthesize(ky, kx, values, m, n, dtype=np.float64):
+    """Re(ifft2) of the two spectra that are zero but at the bins (ky, kx) with ``values`` (2, nb): a (2, m, n)
+    DeviceArray of ``dtype`` (float64 or float32)."""
+    out = DeviceArray((2, m, n), dtype)
+    ky = np.ascontiguousarray(ky, dtype=np.int32)
+    kx = np.ascontiguousarray(kx, dtype=np.int32)
+    vals = np.ascontiguousarray(values, dtype=np.complex128)
+    _lib.check(_lib.lib().psh_darts_synth_dev(ky.ctypes.data_as(ctypes.c_void_p), kx.ctypes.data_as(ctypes.c_void_p),
+                                              vals.ctypes.data_as(ctypes.c_void_p), int(ky.size), m, n,
+                                              int(np.dtype(dtype) == np.float32), out.ptr), "psh_darts_synth_dev")
+    return out
+
+
+def _frames_on_device(input_images):
+    if isinstance(input_images, DeviceArray):
+        if input_images.dtype not in (np.float32, np.float64):
+            raise ValueError("device-resident DARTS input must be float32 or float64 (got %s)" % input_images.dtype)
+        return input_images
+    arr = np.asarray(input_images)
+    dtype = np.float32 if arr.dtype == np.float32 else np.float64
+    return DeviceArray.from_host(np.ascontiguousarray(arr, dtype=dtype))
+
+
+def _nonfinite(frames):
+    flag = ctypes.c_int(0)
+    _lib.check(_lib.lib().psh_darts_nonfinite_dev(frames.ptr, int(frames.dtype == np.float32), frames.size,
+                                                  ctypes.byref(flag)), "psh_darts_nonfinite_dev")
+    return bool(flag.value)
+
+
+def DARTS(input_images, **kwargs):
+    """Compute the advection field from a sequence of input images with the DARTS method (reference:
+    pysteps/motion/darts.py; keywords, defaults, checks, printed lines and return value as documented there).
+
+    ``input_images``: (T, m, n) NumPy array or DeviceArray.  Returns ``np.stack([U, V])``: (2, m, n) float64 for
+    ``output_type="spatial"``, the two (2 M_y + 1, 2 M_x + 1) complex128 coefficient arrays for ``"spectral"``.
+    A DeviceArray input gives a DeviceArray output (float32 for float32 frames)."""
+    _check_ndim(input_images)
+    o = _options(kwargs)
+    T = input_images.shape[0]
+    if o["N_t"] >= T - 1:
+        raise ValueError("N_t = %d >= %d = T-1, but N_t < T-1 required" % (o["N_t"], T - 1))
+    if o["output_type"] not in ["spatial", "spectral"]:
+        raise ValueError("invalid output_type=%s, must be 'spatial' or 'spectral'" % o["output_type"])
+
+    why = _unsupported(tuple(input_images.shape), o)
+    if why is not None:
+        ref = _reference_darts()
+        if ref is None:
+            raise NotImplementedError("pysteps_amd DARTS: %s, and pysteps is not importable for the reference's DARTS"
+                                      % why)
+        warnings.warn("pysteps_amd DARTS: %s - running the reference's DARTS" % why, stacklevel=2)
+        resident = isinstance(input_images, DeviceArray)
+        out = ref(input_images.to_host() if resident else input_images, **kwargs)
+        return DeviceArray.from_host(out) if resident else out
+
+    resident = isinstance(input_images, DeviceArray)
+    if not resident and np.any(~np.isfinite(input_images)):
+        raise ValueError("the input images contain non-finite values")
+    m, n = int(input_images.shape[1]), int(input_images.shape[2])
+    _raise_index_error((m, n, T), o)
+    frames = _frames_on_device(input_images)
+    if resident and _nonfinite(frames):
+        raise ValueError("the input images contain non-finite values")
+
+    verbose = o["verbose"]
+    if verbose:
+        print("Computing the motion field with the DARTS method.")
+        t0 = time.time()
+        print("-----")
+        print("DARTS")
+        print("-----")
+        print("  Computing the FFT of the reflectivity fields...", end="", flush=True)
+        starttime = time.time()
+
+    ev = [Event().record()]
+    cube = band_cube(frames, o["N_y"], o["N_x"], o["N_t"], o["M_y"], o["M_x"])
+    ev.append(Event().record())
+    if verbose:
+        synchronize()
+        print("Done in %.2f seconds." % (time.time() - starttime))
+        # y is formed together with the matrix entries, in the same pass
+        print("  Constructing the y-vector...", end="", flush=True)
+        print("Done in %.2f seconds." % 0.0)
+        print("  Constructing the H-matrix...", end="", flush=True)
+        starttime = time.time()
+
+    shape = (T, m, n)
+    if o["lsq_method"] == 1:
+        M_dev, y_dev = row_matrix(cube, shape, o)
+        M, y = M_dev.to_host(), y_dev.to_host()
+    else:
+        MM, Mhy = gram(cube, shape, o)
+    ev.append(Event().record())
+    if verbose:
+        print("Done in %.2f seconds." % (time.time() - starttime))
+        print("  Solving the linear systems...", end="", flush=True)
+        starttime = time.time()
+
+    t_solve = time.perf_counter()
+    if o["lsq_method"] == 1:
+        x = np.linalg.lstsq(M, y, rcond=0.01)[0]
+    else:
+        x, _ = solve_leastsq(MM, Mhy)
+    t_solve = (time.perf_counter() - t_solve) * 1e3
+    if verbose:
+        print("Done in %.2f seconds." % (time.time() - starttime))
+
+    h, w = 2 * o["M_y"] + 1, 2 * o["M_x"] + 1
+    V = np.ascontiguousarray(x[0 : h * w]).reshape(h, w).astype(complex)
+    U = np.ascontiguousarray(x[h * w : 2 * h * w]).reshape(h, w).astype(complex)
+
+    ev.append(Event().record())
+    if o["output_type"] == "spatial":
+        ky, kx, vals = fill_bins(U, V, m, n, o["M_y"], o["M_x"])
+        dtype = np.float32 if resident and frames.dtype == np.float32 else np.float64
+        out = synthesize(ky, kx, vals, m, n, dtype)
+        result = out if resident else out.to_host()
+    else:
+        spec = np.stack([U, V])
+        result = DeviceArray.from_host(spec) if resident else spec
+    ev.append(Event().record())
+    synchronize()
+
+    last_run_stats.clear()
+    last_run_stats.update(band=ev[0].elapsed_ms(ev[1]), gram=ev[1].elapsed_ms(ev[2]), solve=t_solve,
+                          synth=ev[3].elapsed_ms(ev[4]))
+    last_run_stats["total"] = ev[0].elapsed_ms(ev[4])
+
+    if verbose:
+        print("--- %s seconds ---" % (time.time() - t0))
+
+    return result

@@ -18,6 +18,7 @@ NOISE_NAMES = {"parametric_hip": "parametric", "nonparametric_hip": "nonparametr
 BPS_NAME = "bps_hip"  # vel_pert_method: the reference's generate_bps behind an initialiser that shares the unit fields
 EXTRAPOLATION_NAMES = ("semilagrangian_hip",)
 MOTION_NAMES = ("lk_hip", "lucaskanade_hip")
+DARTS_NAME = "darts_hip"  # the stock "darts" stays the reference's, with or without override
 FEATURE_NAMES = {"blob_hip": "blob", "shitomasi_hip": "shitomasi"}  # pysteps.feature.get_method(...)
 _STOCK_EXTRAPOLATION = ("semilagrangian",)
 _STOCK_MOTION = ("lk", "lucaskanade")
@@ -26,6 +27,7 @@ _STOCK_MOTION = ("lk", "lucaskanade")
 def register_into(motion_methods, extrapolation_methods, override=False):
     """Insert the callables into the given dicts (either may be None). Returns the names added."""
     from .extrapolation.semilagrangian import extrapolate
+    from .motion.darts import DARTS
     from .motion.lucaskanade import dense_lucaskanade
 
     added = []
@@ -37,6 +39,8 @@ def register_into(motion_methods, extrapolation_methods, override=False):
         for name in MOTION_NAMES + (_STOCK_MOTION if override else ()):
             motion_methods[name] = dense_lucaskanade
             added.append("motion:" + name)
+        motion_methods[DARTS_NAME] = DARTS
+        added.append("motion:" + DARTS_NAME)
     return added
 
 
