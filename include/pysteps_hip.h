@@ -338,6 +338,18 @@ int psh_anvil_update_dev(double *ring_dev, const double *phi_dev, int n_levels, 
                          const unsigned char *mask_dev, const unsigned char *rr_mask_dev, const double *a_dev,
                          const double *b_dev, double *out_dev);
 
+/* ---- the Lagrangian probability nowcast (csrc/lagprob.hip) ------------------------------------------------------ *
+ * pysteps/nowcasts/lagrangian_probability.py behind the extrapolator: for each of the T planes (m, n) of an advected
+ * stack, float32 or float64 (fields_f64), the fraction of the valid (not NaN) pixels under the plane's kernel whose
+ * value is >= threshold, as float64, NaN where the plane is NaN.  The kernel of plane i has scales_host[i] rows
+ * (1 .. 255); row t of it covers the input pixels (y + t + c - scale + 1, x + lo .. x + hi) of output pixel (y, x),
+ * c = (scale - 1) / 2, with lo / hi taken from span_lo_host / span_hi_host, the tables of all planes one after the
+ * other (sum of the scales entries each; c - scale <= lo, lo <= hi + 1, hi <= c).  Pixels outside the image count
+ * for nothing.  Both counts are exact integers and the quotient is correctly rounded.  Widths above 65535 are
+ * PSH_EUNSUPPORTED.  Queued on the library stream; the tables are consumed before the call returns. */
+int psh_lagprob_dev(const void *fields_dev, int fields_f64, int T, int m, int n, double threshold, const int *scales_host,
+                    const int *span_lo_host, const int *span_hi_host, double *out_dev);
+
 /* ---- the DARTS motion estimate (csrc/darts.hip) ---------------------------------------------------------------- *
  * pysteps/motion/darts.py: the spectral band of the frames, the normal equations and the dense field; the small
  * solve stays on the host.  K_y = N_y + M_y, K_x = N_x + M_x; every call is queued on the library stream.

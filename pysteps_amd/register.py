@@ -229,14 +229,18 @@ def unpatch_dilated_mask():
 
 
 def register_nowcasts():
-    """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) to pysteps' nowcast table
-    (pysteps/nowcasts/interface.py ``_nowcast_methods``); the stock ``"anvil"`` stays the reference's."""
+    """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) and ``"lagrangian_probability_hip"``
+    (:func:`pysteps_amd.nowcasts.lagrangian_probability.forecast`) to pysteps' nowcast table
+    (pysteps/nowcasts/interface.py ``_nowcast_methods``); the stock ``"anvil"`` and ``"lagrangian_probability"`` stay
+    the reference's."""
     import pysteps.nowcasts.interface as now_if  # noqa: PLC0415
 
     from .nowcasts.anvil import forecast  # noqa: PLC0415
+    from .nowcasts.lagrangian_probability import forecast as lagprob_forecast  # noqa: PLC0415
 
     now_if._nowcast_methods["anvil_hip"] = forecast
-    return ["nowcast:anvil_hip"]
+    now_if._nowcast_methods["lagrangian_probability_hip"] = lagprob_forecast
+    return ["nowcast:anvil_hip", "nowcast:lagrangian_probability_hip"]
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
