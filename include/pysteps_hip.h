@@ -350,6 +350,22 @@ int psh_anvil_update_dev(double *ring_dev, const double *phi_dev, int n_levels, 
 int psh_lagprob_dev(const void *fields_dev, int fields_f64, int T, int m, int n, double threshold, const int *scales_host,
                     const int *span_lo_host, const int *span_hi_host, double *out_dev);
 
+/* ---- ensemble mean and exceedance probabilities (csrc/ensstats.hip) ---------------------------------------------- *
+ * pysteps/postprocessing/ensemblestats.py mean / excprob of a member stack (k, npix), float32 or float64
+ * (members_f64), in ONE pass over the members: any subset of
+ *   mean_dev   (npix) the ensemble mean: the sum in member order in the members' type - or in float64 for float32
+ *              members with accumulate_f64, the mean of the widened members - divided by k; with mean_ignore_nan or
+ *              mean_has_thr (values < mean_thr count as NaN) NaN adds nothing to the sum or the count, 0 / 0 = NaN.
+ *              float32 for float32 members without accumulate_f64, else float64.  NULL: not wanted.
+ *   probs_dev  (n_thresholds, npix) float64, n_thresholds <= 16: #{finite and >= threshold} / k, NaN where a member is
+ *              not finite; with prob_ignore_nan over the finite members, NaN where there is none.  Comparison as in
+ *              float64.  NULL: not wanted.
+ * Bit-identical with NumPy's axis-0 reductions on a C-contiguous stack.  Queued on the library stream; the threshold
+ * list is consumed before the call returns. */
+int psh_ens_products_dev(const void *members_dev, int members_f64, int k, size_t npix, const double *thresholds_host,
+                         int n_thresholds, int prob_ignore_nan, int mean_ignore_nan, int mean_has_thr, double mean_thr,
+                         int accumulate_f64, void *mean_dev, double *probs_dev);
+
 /* ---- the DARTS motion estimate (csrc/darts.hip) ---------------------------------------------------------------- *
  * pysteps/motion/darts.py: the spectral band of the frames, the normal equations and the dense field; the small
  * solve stays on the host.  K_y = N_y + M_y, K_x = N_x + M_x; every call is queued on the library stream.

@@ -264,8 +264,11 @@ class _BatchedLoop:
         self.velocity, self.perts, self.opts = velocity, perturbators, opts
         self.adv = None
         self.timeline = None
+        self.moved = None  # float32 DeviceArray of the members advected last from resident fields
 
-    def advect(self, fields, n_members, dt, t_total, sink=None):
+    def advect(self, fields, n_members, dt, t_total, sink=None, on_device=False):
+        """``on_device`` (resident fields only): no download - the float32 stack of the advected members is returned as
+        the advector left it in HBM.  It is valid until the next call (the advector may reuse it)."""
         if self.adv is None:
             self.adv = EnsembleAdvector(self.velocity, n_members, self.perts, **self.opts)
         lead = None if self.perts is None else t_total * self.perts[0]["time_scale"]  # minutes
@@ -280,6 +283,9 @@ class _BatchedLoop:
             moved = self.adv.step(f32, dt, lead)
             if self.timeline is not None:
                 self.timeline.mark("advect")
+            self.moved = moved
+            if on_device and sink is None:
+                return moved
             if sink is not None:
                 # straight into the caller's (n_members, n_timesteps, m, n) result block: widened on the
                 # device, one queued copy per member, nobody waits here
@@ -306,7 +312,13 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
     """Same parameters, call order and return value as the reference (utils.py:265-345): a list /
     array of forecast fields ``(n_timesteps, m, n)`` or ``(n_members, n_timesteps, m, n)``, with the
     loop time when ``measure_time`` is set.  ``num_workers`` is accepted; the members are advanced
-    together on the GPU instead of by worker threads."""
+    together on the GPU instead of by worker threads.
+
+    A ``callback`` with a truthy ``accepts_device`` attribute (``postprocessing.ensemblestats.EnsembleProducts``) is
+    called with the float32 ``DeviceArray`` ``(n_members, m, n)`` of the advected members while the loop runs the
+    resident update with the member-batched advection - valid during the call only, the advector may reuse it - and
+    with ``return_output=False`` no member is then widened or copied to the host (``last_run_stats`` has a ``callback``
+    and no ``download`` phase).  In every other case such a callback gets the host stack like any other."""
     started = time.time()  # like the reference (utils.py:347): set-up of the loop is part of its time
     plan = _time_bins(timesteps)
     extrap_kwargs = {} if extrap_kwargs is None else dict(extrap_kwargs)
@@ -379,6 +391,11 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
             block = _pinned.empty((n_members, n_out) + tuple(precip.shape), np.float64)
             if timeline is not None:
                 timeline.mark("result_block")
+    # a callback that takes the members where they lie (``accepts_device``, e.g. postprocessing.ensemblestats.EnsembleProducts)
+    # gets the float32 DeviceArray (n_members, m, n) the advector returned instead of np.stack(advected); it is valid
+    # during the call only, the advector may reuse it.  With return_output=False no member is widened or downloaded
+    device_callback = (callback is not None and bool(getattr(callback, "accepts_device", False))
+                       and resident is not None and isinstance(engine, _BatchedLoop))
     out_index = 0
     t_prev = t_total = 0.0
     try:
@@ -409,14 +426,19 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
                 if block is not None:
                     advected = engine.advect(fields, fields.shape[0], dt, t_total, sink=block[:, out_index])
                     out_index += 1
-                    if callback is not None:
+                    if callback is not None and not device_callback:
                         _lib.check(_lib.lib().psh_sync(), "psh_sync")
+                elif device_callback and isinstance(fields, DeviceArray) and not return_output:
+                    advected = engine.advect(fields, fields.shape[0], dt, t_total, on_device=True)
                 else:
                     advected = engine.advect(fields, fields.shape[0], dt, t_total)
                     if return_output:
                         for j, a in enumerate(advected):
                             outputs[j].append(a)
-                if callback is not None:
+                if device_callback and isinstance(fields, DeviceArray):
+                    callback(engine.moved)
+                    timeline.mark("callback")
+                elif callback is not None:
                     callback(np.stack(advected))
                 t_prev = t_sub
             if not subtimesteps:  # no lead time in this bin: displacement only, up to the next integer step

@@ -20,6 +20,7 @@ EXTRAPOLATION_NAMES = ("semilagrangian_hip",)
 MOTION_NAMES = ("lk_hip", "lucaskanade_hip")
 DARTS_NAME = "darts_hip"  # the stock "darts" stays the reference's, with or without override
 FEATURE_NAMES = {"blob_hip": "blob", "shitomasi_hip": "shitomasi"}  # pysteps.feature.get_method(...)
+POSTPROCESSING_NAMES = {"mean": "mean", "excprob": "excprob"}  # pysteps.postprocessing.get_method(name + "_hip", "ensemblestats")
 _STOCK_EXTRAPOLATION = ("semilagrangian",)
 _STOCK_MOTION = ("lk", "lucaskanade")
 
@@ -243,6 +244,23 @@ def register_nowcasts():
     return ["nowcast:anvil_hip", "nowcast:lagrangian_probability_hip"]
 
 
+def register_postprocessing(override=False):
+    """Add ``"mean_hip"`` and ``"excprob_hip"`` (:mod:`pysteps_amd.postprocessing.ensemblestats`) to pysteps' ensemble
+    statistics table (pysteps/postprocessing/interface.py ``_ensemblestats_methods``:
+    ``pysteps.postprocessing.get_method("excprob_hip", "ensemblestats")``); the stock ``"mean"`` and ``"excprob"`` are
+    only replaced with ``override``.  ``"banddepth"`` stays the reference's (its ties are broken at random)."""
+    import pysteps.postprocessing.interface as post_if  # noqa: PLC0415
+
+    from .postprocessing import ensemblestats  # noqa: PLC0415
+
+    added = []
+    for name, fn in POSTPROCESSING_NAMES.items():
+        for key in (name + "_hip",) + ((name,) if override else ()):
+            post_if._ensemblestats_methods[key] = getattr(ensemblestats, fn)
+            added.append("ensemblestats:" + key)
+    return added
+
+
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
              dilated_mask=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
@@ -269,6 +287,10 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += register_nowcasts()
     except ImportError:
         pass  # pysteps.nowcasts imports every nowcast module; a stripped-down install may lack one's dependencies
+    try:
+        added += register_postprocessing(override=override)
+    except ImportError:
+        pass  # pysteps.postprocessing imports its diagnostics' optional dependencies lazily; a stripped-down install may lack it
     if fft:
         added += register_fft()
         added += register_spectral()
