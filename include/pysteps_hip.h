@@ -366,6 +366,21 @@ int psh_ens_products_dev(const void *members_dev, int members_f64, int k, size_t
                          int n_thresholds, int prob_ignore_nan, int mean_ignore_nan, int mean_has_thr, double mean_thr,
                          int accumulate_f64, void *mean_dev, double *probs_dev);
 
+/* ---- the fractions skill score (csrc/fss.hip) -------------------------------------------------------------------- *
+ * pysteps/verification/spatialscores.py fss_accum for K forecasts (K, m, n), float32 or float64 (fct_f64), against one
+ * observation (m, n) shared by all of them (obs_shared) or a stack (K, m, n), float32 or float64 (obs_f64), for
+ * n_thresholds thresholds and n_scales scales in one call.  A pixel counts when it is finite and >= the threshold;
+ * forecasts are compared with thr_fct_host[t] and observations with thr_obs_host[t], both as float64 (the caller
+ * decides what a threshold stands for against a float32 field).  With c_f and c_o the counts in the s x s window of
+ * scipy.ndimage.uniform_filter(size = s, mode = "constant") - rows y - s / 2 .. y - s / 2 + s - 1 and the same
+ * columns, clipped to the image - out_dev (K, n_thresholds, n_scales, 3) receives sum(c_f^2), sum(c_f c_o) and
+ * sum(c_o^2) over the image: exact integers, the same in every run; the reference's sums are these over s^4.  A scale
+ * <= 1 is the 0/1 map itself.  Scales that are not integers or exceed 255 and shapes above 65535 either way are
+ * PSH_EUNSUPPORTED.  Queued on the library stream; the host tables are consumed before the call returns. */
+int psh_fss_sums_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int obs_f64, int obs_shared, int K, int m, int n,
+                     const double *thr_fct_host, const double *thr_obs_host, int n_thresholds, const double *scales_host,
+                     int n_scales, unsigned long long *out_dev);
+
 /* ---- the DARTS motion estimate (csrc/darts.hip) ---------------------------------------------------------------- *
  * pysteps/motion/darts.py: the spectral band of the frames, the normal equations and the dense field; the small
  * solve stays on the host.  K_y = N_y + M_y, K_x = N_x + M_x; every call is queued on the library stream.

@@ -101,6 +101,8 @@ SIGNATURES = {
     "psh_lagprob_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psh_ens_products_dev": (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_int, c_int, c_int, c_int, c_double, c_int,
                                      c_void_p, c_void_p]),
+    "psh_fss_sums_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                 c_int, c_void_p]),
     "psh_darts_nonfinite_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     "psh_darts_band_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "psh_darts_gram_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p]),

@@ -5,7 +5,7 @@
 // 0/1 disc (a square below scale 5) and divides them.  Every output is therefore the quotient of two small integers;
 // the kernels here count them instead of convolving:
 //   lagprob_prefix  per row the exclusive prefix counts of both maps, packed as two 16-bit halves of one uint32
-//                   (exceed low, valid high), rows of n + 1 words with a leading zero.  Both prefixes are monotone, so
+//                   (exceed low, valid high), rows of n + 1 words with a leading zero (the scan of row_prefix.h).  Both prefixes are monotone, so
 //                   a difference of two packed words never borrows, and a disc of diameter <= 255 sums to < 65536
 //                   per half.
 //   lagprob_count   a workgroup owns a 64 x 16 output tile and walks the scale + 15 prefix rows it needs in chunks of
@@ -17,12 +17,13 @@
 // Integer throughout, no atomics, no data-dependent loops: the result is deterministic and equals the correctly rounded
 // quotient of the two counts.
 #include "common.h"
+#include "row_prefix.h"
 
 namespace psh {
 namespace {
 
 constexpr int kLagMaxScale = 255;
-constexpr int kLagMaxWidth = 65535;  // a packed row prefix has 16 bits per map
+constexpr int kLagMaxWidth = kPackedPrefixMaxWidth;  // a packed row prefix has 16 bits per map
 constexpr int kLagThreads = 256;
 constexpr int kLagTileW = 64;   // output columns of a workgroup = lanes of a wave
 constexpr int kLagRowsPerWave = 4;
@@ -39,39 +40,14 @@ template <typename T>
 __global__ __launch_bounds__(kLagThreads) void lagprob_prefix(const T *__restrict__ field, int n, double threshold,
                                                                uint32_t *__restrict__ prefix) {
   __shared__ uint32_t wave_sum[kLagThreads / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t row = blockIdx.x;
   const T *src = field + row * n;
-  uint32_t *dst = prefix + row * (static_cast<size_t>(n) + 1);
-  if (tid == 0) dst[0] = 0u;
-  uint32_t carry = 0u;
-  for (int base = 0; base < n; base += kLagThreads) {
-    const int x = base + tid;
-    uint32_t v = 0u;
-    if (x < n) {
-      const T f = src[x];
-      const bool valid = !(f != f);
-      const bool exceed = valid && static_cast<double>(f) >= threshold;
-      v = (exceed ? 1u : 0u) | (valid ? 0x10000u : 0u);
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t u = __shfl_up(v, d, 64);
-      if (lane >= d) v += u;
-    }
-    if (lane == 63) wave_sum[wave] = v;
-    __syncthreads();
-    uint32_t before = carry, total = 0u;
-#pragma unroll
-    for (int w = 0; w < kLagThreads / 64; ++w) {
-      const uint32_t s = wave_sum[w];
-      if (w < wave) before += s;
-      total += s;
-    }
-    if (x < n) dst[x + 1] = v + before;
-    carry += total;
-    __syncthreads();
-  }
+  packed_row_prefix<kLagThreads>(n, prefix + row * (static_cast<size_t>(n) + 1), wave_sum, [&](int x) {
+    const T f = src[x];
+    const bool valid = !(f != f);
+    const bool exceed = valid && static_cast<double>(f) >= threshold;
+    return (exceed ? 1u : 0u) | (valid ? 0x10000u : 0u);
+  });
 }
 
 template <typename T>

@@ -229,6 +229,36 @@ def unpatch_dilated_mask():
         del ref_mod._reference_compute_dilated_mask
 
 
+def patch_fss():
+    """Replace ``fss`` and ``fss_accum`` of ``pysteps.verification.spatialscores`` by the device versions
+    (:mod:`pysteps_amd.verification.spatialscores`).  ``pysteps.verification.interface.get_method`` is an if-chain that
+    imports ``fss`` from that module when it is called (interface.py:169), so there is no table to add a name to and the
+    attributes are what has to change; ``get_method("fss")`` and the reference's own ``fss`` (which calls the module's
+    ``fss_accum``) then count on the device.  Inputs the device path declines run the reference's ``fss_accum``."""
+    import pysteps.verification.spatialscores as ref_mod  # noqa: PLC0415
+
+    from .verification import spatialscores as hip_mod  # noqa: PLC0415
+
+    if ref_mod.fss_accum is hip_mod.fss_accum:
+        return []
+    ref_mod._reference_fss, ref_mod._reference_fss_accum = ref_mod.fss, ref_mod.fss_accum
+    hip_mod._reference_fss_accum = ref_mod.fss_accum
+    ref_mod.fss, ref_mod.fss_accum = hip_mod.fss, hip_mod.fss_accum
+    return ["verification:fss", "verification:fss_accum"]
+
+
+def unpatch_fss():
+    """Undo :func:`patch_fss`."""
+    import pysteps.verification.spatialscores as ref_mod  # noqa: PLC0415
+
+    from .verification import spatialscores as hip_mod  # noqa: PLC0415
+
+    if getattr(ref_mod, "_reference_fss_accum", None) is not None:
+        ref_mod.fss, ref_mod.fss_accum = ref_mod._reference_fss, ref_mod._reference_fss_accum
+        del ref_mod._reference_fss, ref_mod._reference_fss_accum
+    hip_mod._reference_fss_accum = None
+
+
 def register_nowcasts():
     """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) and ``"lagrangian_probability_hip"``
     (:func:`pysteps_amd.nowcasts.lagrangian_probability.forecast`) to pysteps' nowcast table
@@ -262,7 +292,7 @@ def register_postprocessing(override=False):
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
-             dilated_mask=False):
+             dilated_mask=False, fss=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -274,7 +304,10 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     history as spectra and reproduces the reference's fields up to rounding, not bit for bit (identical NaN
     masks, no pixel decided differently by a threshold or a rank in the tests, 8e-8 relative L2 end to end);
     ``PYSTEPS_HIP_RESIDENT_DOMAIN=spatial`` selects the chain of spatial operators whose element-wise steps
-    are bit-identical with the reference's.  :func:`unpatch_main_loop` restores the reference loop."""
+    are bit-identical with the reference's.  :func:`unpatch_main_loop` restores the reference loop.
+
+    ``fss=True`` makes ``pysteps.verification`` count the fractions skill score on the device (:func:`patch_fss`;
+    :func:`unpatch_fss` undoes it)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -300,6 +333,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += patch_autoregression()
     if dilated_mask:
         added += patch_dilated_mask()
+    if fss:
+        added += patch_fss()
     if patch_main_loop:
         import importlib  # noqa: PLC0415
 
