@@ -121,14 +121,20 @@ struct TopK {
     worst_pos = 0;
   }
 
+  // The slot to evict is the LAST entry in (distance, sample index) order: among equal maxima the one with the
+  // highest index.  Samples are offered in index order and one AT the running maximum is turned away, so the set
+  // always holds the k first samples of that order - at equidistant samples the lower indices, as add_nearest and
+  // idw_small_ring2 take them; the field does not depend on which path a tile took.
+
   // recompute the running maximum after slots were written directly
   __device__ __forceinline__ void refresh() {
     float w = -INFINITY;
-    int wp = 0;
+    int wi = -1, wp = 0;
 #pragma unroll
     for (int j = 0; j < KMAX; ++j) {
-      if (d2[j] > w) {
+      if (d2[j] > w || (d2[j] == w && idx[j] > wi)) {
         w = d2[j];
+        wi = idx[j];
         wp = j;
       }
     }
@@ -139,14 +145,15 @@ struct TopK {
   __device__ __forceinline__ void offer(float d, int i) {
     if (d < worst) {
       float w = -INFINITY;
-      int wp = 0;
+      int wi = -1, wp = 0;
 #pragma unroll
       for (int j = 0; j < KMAX; ++j) {
         const bool hit = j == worst_pos;
         d2[j] = hit ? d : d2[j];
         idx[j] = hit ? i : idx[j];
-        if (d2[j] > w) {
+        if (d2[j] > w || (d2[j] == w && idx[j] > wi)) {
           w = d2[j];
+          wi = idx[j];
           wp = j;
         }
       }

@@ -5,6 +5,8 @@ single sample / uniform values -> uniform field, k=1, k=None).  Tolerance: the
 kernel computes in float32 -> relative L2 <= 1e-5 against the float64 reference,
 max abs <= 1e-4 px/step; pixels whose k-th and (k+1)-th neighbours are exactly
 equidistant are excluded (the tie order is implementation-defined in cKDTree too).
+Those pixels are held exactly, none left out, in tests/test_idw_ties_gpu.py (integer, half- and quarter-integer
+sample positions against the brute-force oracle of tests/helpers/idw_exact.py).
 """
 
 import os
