@@ -609,6 +609,10 @@ int psh_cascade_decompose_dev(const double *field_dev, const double *weights_dev
  * decomposition.py:224-232 is applied by the consumer, psh_steps_ar_recompose_raw_dev, on the way in. */
 int psh_cascade_decompose_stats_dev(const double *field_dev, const double *weights_dev, int nlevels, int m, int n,
                                     double *levels_dev, double *stats_dev);
+/* The levels alone, as the transforms produce them: no statistics pass (the caller takes its own, e.g. over a mask
+ * with psh_masked_moments_dev).  Asynchronous. */
+int psh_cascade_decompose_levels_dev(const double *field_dev, const double *weights_dev, int nlevels, int m, int n,
+                                     double *levels_dev);
 int psh_cascade_recompose_dev(const double *levels_dev, int nlevels, int m, int n, const double *means_host,
                               const double *stds_host, double field_mean, double *out_dev);
 int psh_noise_filter_dev(const double *white_dev, const double *filter_dev, int m, int n, double *out_dev);
@@ -745,6 +749,38 @@ int psh_steps_mean_shift_dev(double *field_dev, size_t n, double threshold, doub
 int psh_ge_mask_dev(const double *field_dev, size_t n, double threshold, unsigned char *out_dev);
 int psh_nan_where_dev(double *field_dev, const unsigned char *mask_dev, size_t n);
 int psh_lerp_dev(const double *a_dev, const double *b_dev, double w, double *out_dev, size_t n);
+
+/* ---- the noise standard-deviation adjustment of STEPS (csrc/noise_adj.hip) -------------------------------- *
+ * pysteps/noise/utils.py:24-135 (compute_noise_stddev_adjs) between the noise filter and the cascade decomposition,
+ * and the level statistics it compares.  float64; every reduction is block partial sums finished by one block in a
+ * fixed order (no floating-point atomics): identical bits from run to run and for any batch size.  Asynchronous.
+ *  psh_noise_adj_observed_dev  utils.py:83-87: mask[i] = R[i] >= thr1 (uint8, NaN -> 0); clean[i] = R[i] where the
+ *      mask is set and R[i] is finite, thr2 elsewhere
+ *  psh_noise_adj_centre_dev    utils.py:92: field[i] -= mu
+ *  psh_noise_adj_prepare_dev   utils.py:113-118 on nbatch filtered noise fields (nbatch, plane), in place, the
+ *      reference's operations in its order, each rounded on its own: N / std(N) * sigma + mu; thr2 where the mask
+ *      (plane bytes, shared by the batch) is 0; - mu.  std(N): population standard deviation per field;
+ *      stats_out_dev (may be NULL) receives the nbatch (mean, std) pairs that were used
+ *  psh_mask_count_dev          *count_dev = number of non-zero bytes of the mask
+ *  psh_masked_moments_dev      stats[p] = (np.mean(x_p[mask]), np.std(x_p[mask])) (cascade/decomposition.py:223-228)
+ *      of nplanes planes (nplanes, plane); count_dev from psh_mask_count_dev of the same mask (computed once per mask);
+ *      sums carried in double-double with a zero shift; planes_per_block 1, or 4: four planes share one read of the
+ *      mask - the same bits either way.  An empty mask gives NaN like NumPy
+ *  psh_spectrum_level_moments_dev  the unmasked level statistics off nspec half spectra (nspec, m, n/2+1) complex128
+ *      and the band-pass weights (nlevels <= 16, m, n/2+1): stats[s][k] = (X[0,0] W_k[0,0] / (m n),
+ *      sqrt(sum' h |X W_k|^2) / (m n)), h = 1 on column 0 and on the Nyquist column of an even n, 2 elsewhere, the DC
+ *      term left out (pysteps/utils/spectral.py std) - np.mean / np.std of irfft2(X W_k) without the transform.
+ *      Needs weights that keep X W_k Hermitian (functions of |k|) */
+int psh_noise_adj_observed_dev(const double *r_dev, size_t plane, double thr1, double thr2, unsigned char *mask_dev,
+                               double *clean_dev);
+int psh_noise_adj_centre_dev(double *field_dev, size_t n, double mu);
+int psh_noise_adj_prepare_dev(double *fields_dev, int nbatch, size_t plane, const unsigned char *mask_dev, double sigma,
+                              double mu, double thr2, double *stats_out_dev);
+int psh_mask_count_dev(const unsigned char *mask_dev, size_t plane, unsigned long long *count_dev);
+int psh_masked_moments_dev(const double *planes_dev, int nplanes, size_t plane, const unsigned char *mask_dev,
+                           const unsigned long long *count_dev, int planes_per_block, double *stats_dev);
+int psh_spectrum_level_moments_dev(const void *spec_dev, int nspec, const double *weights_dev, int nlevels, int m, int n,
+                                   double *stats_dev);
 
 /* ---- numpy.random.RandomState.randn on the device (csrc/rng.hip) ------------------ *
  * The white noise of the STEPS member loop: pysteps/noise/fftgenerators.py:400 draws

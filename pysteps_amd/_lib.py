@@ -78,9 +78,16 @@ SIGNATURES = {
     "psh_cascade_decompose_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                           POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "psh_cascade_decompose_stats_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "psh_cascade_decompose_levels_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "psh_cascade_recompose_dev": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double),
                                           c_double, c_void_p]),
     "psh_noise_filter_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "psh_noise_adj_observed_dev": (c_int, [c_void_p, c_size_t, c_double, c_double, c_void_p, c_void_p]),
+    "psh_noise_adj_centre_dev": (c_int, [c_void_p, c_size_t, c_double]),
+    "psh_noise_adj_prepare_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_double, c_double, c_double, c_void_p]),
+    "psh_mask_count_dev": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "psh_masked_moments_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
+    "psh_spectrum_level_moments_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "psh_probmatch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "psh_probmatch_async_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "psh_probmatch_status": (c_int, [c_int]),

@@ -149,6 +149,9 @@ __global__ __launch_bounds__(kRedThreads) void ar_iterate(const double *__restri
   }
 }
 
+}  // namespace
+
+// {mean, population std} of `planes` planes (declared in common.h: noise_adj.hip standardises with it too)
 int moments(const double *x_dev, int planes, size_t plane, double2 *stats_dev, hipStream_t stream) {
   void *partial = nullptr;
   if (int rc = psh_malloc(&partial, static_cast<size_t>(planes) * kRedBlocksF64 * sizeof(double2))) return rc;
@@ -162,15 +165,16 @@ int moments(const double *x_dev, int planes, size_t plane, double2 *stats_dev, h
   return PSH_OK;
 }
 
-}  // namespace
 }  // namespace psh
 
 using psh::fail;
 
-// stats_out_dev (nullable): the level statistics (mean, std per level: nlevels double2) stay on the device
+// stats_out_dev (nullable): the level statistics (mean, std per level: nlevels double2) stay on the device;
+// levels_only: the transforms alone, no statistics pass (the caller takes its own, over a mask)
 static int cascade_decompose_run(const double *field_dev, const double *weights_dev, int nlevels, int m, int n,
                                  int normalize, int subtract_mean, double *levels_dev, double *means_host,
-                                 double *stds_host, double *field_mean_host, double *stats_out_dev) {
+                                 double *stds_host, double *field_mean_host, double *stats_out_dev,
+                                 bool levels_only = false) {
   PSH_REQUIRE_INIT();
   if (!field_dev || !weights_dev || !levels_dev) return fail(PSH_EINVAL, "cascade_decompose: NULL pointer");
   if ((means_host == nullptr) != (stds_host == nullptr))
@@ -208,6 +212,7 @@ static int cascade_decompose_run(const double *field_dev, const double *weights_
                                             levels_dev + static_cast<size_t>(k) * plane, scratch))
         return rc;
     }
+    if (levels_only) return PSH_OK;
     if (int rc = psh::moments(levels_dev, nlevels, plane, stats, c.stream)) return rc;  // :217-232
     if (stats_out_dev)
       PSH_HIP(hipMemcpyAsync(stats_out_dev, stats, static_cast<size_t>(nlevels) * sizeof(double2), hipMemcpyDeviceToDevice, c.stream));
@@ -244,6 +249,12 @@ extern "C" int psh_cascade_decompose_stats_dev(const double *field_dev, const do
                                                int n, double *levels_dev, double *stats_dev) {
   if (!stats_dev) return fail(PSH_EINVAL, "cascade_decompose_stats: NULL pointer");
   return cascade_decompose_run(field_dev, weights_dev, nlevels, m, n, 0, 0, levels_dev, nullptr, nullptr, nullptr, stats_dev);
+}
+
+// the levels alone: no statistics pass at all (psh_masked_moments_dev takes them over the wet pixels)
+extern "C" int psh_cascade_decompose_levels_dev(const double *field_dev, const double *weights_dev, int nlevels, int m,
+                                                int n, double *levels_dev) {
+  return cascade_decompose_run(field_dev, weights_dev, nlevels, m, n, 0, 0, levels_dev, nullptr, nullptr, nullptr, nullptr, true);
 }
 
 extern "C" int psh_cascade_recompose_dev(const double *levels_dev, int nlevels, int m, int n, const double *means_host,

@@ -1,3 +1,4 @@
-"""Noise generators on the HIP path (mirror of pysteps.noise.fftgenerators)."""
+"""Noise generators and the noise adjustment on the HIP path (mirror of pysteps.noise.fftgenerators / .utils)."""
 
 from .fftgenerators import generate_noise_2d_fft_filter  # noqa: F401
+from .utils import compute_noise_stddev_adjs  # noqa: F401

@@ -259,6 +259,37 @@ def unpatch_fss():
     hip_mod._reference_fss_accum = None
 
 
+def patch_noise_stddev_adj():
+    """Replace ``pysteps.noise.utils.compute_noise_stddev_adjs`` by the device version
+    (:mod:`pysteps_amd.noise.utils`).  ``nowcasts.steps`` with ``noise_stddev_adj="auto"`` looks the function up as
+    ``noise.utils.compute_noise_stddev_adjs`` when it is called (nowcasts/steps.py:760) and there is no method table
+    for it, so the module attribute is what has to change; calls the device path declines run the reference's
+    function with a ``RuntimeWarning``."""
+    import pysteps.noise.utils as ref_mod  # noqa: PLC0415
+
+    from .noise import utils as hip_mod  # noqa: PLC0415
+
+    if ref_mod.compute_noise_stddev_adjs is hip_mod.compute_noise_stddev_adjs:
+        return []
+    ref_mod._reference_compute_noise_stddev_adjs = ref_mod.compute_noise_stddev_adjs
+    hip_mod._reference_fn = ref_mod.compute_noise_stddev_adjs
+    ref_mod.compute_noise_stddev_adjs = hip_mod.compute_noise_stddev_adjs
+    return ["noise.utils:compute_noise_stddev_adjs"]
+
+
+def unpatch_noise_stddev_adj():
+    """Undo :func:`patch_noise_stddev_adj`."""
+    import pysteps.noise.utils as ref_mod  # noqa: PLC0415
+
+    from .noise import utils as hip_mod  # noqa: PLC0415
+
+    ref = getattr(ref_mod, "_reference_compute_noise_stddev_adjs", None)
+    if ref is not None:
+        ref_mod.compute_noise_stddev_adjs = ref
+        del ref_mod._reference_compute_noise_stddev_adjs
+    hip_mod._reference_fn = None
+
+
 def register_nowcasts():
     """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) and ``"lagrangian_probability_hip"``
     (:func:`pysteps_amd.nowcasts.lagrangian_probability.forecast`) to pysteps' nowcast table
@@ -292,7 +323,7 @@ def register_postprocessing(override=False):
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
-             dilated_mask=False, fss=False):
+             dilated_mask=False, fss=False, noise_stddev_adj=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -307,7 +338,9 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     are bit-identical with the reference's.  :func:`unpatch_main_loop` restores the reference loop.
 
     ``fss=True`` makes ``pysteps.verification`` count the fractions skill score on the device (:func:`patch_fss`;
-    :func:`unpatch_fss` undoes it)."""
+    :func:`unpatch_fss` undoes it).  ``noise_stddev_adj=True`` makes ``nowcasts.steps(noise_stddev_adj="auto")``
+    compute its adjustment coefficients on the device (:func:`patch_noise_stddev_adj`;
+    :func:`unpatch_noise_stddev_adj` undoes it)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -335,6 +368,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += patch_dilated_mask()
     if fss:
         added += patch_fss()
+    if noise_stddev_adj:
+        added += patch_noise_stddev_adj()
     if patch_main_loop:
         import importlib  # noqa: PLC0415
 
