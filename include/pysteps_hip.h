@@ -381,6 +381,29 @@ int psh_fss_sums_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int 
                      const double *thr_fct_host, const double *thr_obs_host, int n_thresholds, const double *scales_host,
                      int n_scales, unsigned long long *out_dev);
 
+/* ---- deterministic verification scores (csrc/detscores.hip) ------------------------------------------------------- *
+ * pysteps/verification/detcatscores.py det_cat_fct_accum and detcontscores.py det_cont_fct_accum for K forecasts of npix
+ * contiguous pixels each, float32 or float64 (fct_f64), against one observation of npix pixels shared by all of them
+ * (obs_shared) or a stack of K, float32 or float64 (obs_f64) on its own.  Both are queued on the library stream and
+ * return the same bits in every run, for every split of a stack into calls and at every alignment of a member.
+ *
+ * psh_detcat_counts_dev: forecasts are compared with thr_fct_host[t] and observations with thr_obs_host[t], both as
+ * float64 (the caller decides what a threshold stands for against a float32 field); an event is value > threshold, NaN
+ * compares false.  out_dev (K, n_thresholds, 4) receives hits, misses, false alarms and correct negatives; the four add
+ * up to npix.  The host tables are consumed before the call returns.
+ *
+ * psh_detcont_sums_dev: conditioning 0 takes every pixel, 1 ("single") those with pred > thr_fct or obs > thr_obs, 2
+ * ("double") those with both; an excluded pixel is NaN on both sides.  counts_dev (K, 4) receives the numbers of finite
+ * observations, finite predictions, pairs with a finite residual, and values of the input that are +-inf (the caller
+ * declines when there are any).  sums_dev (K, 11, 2) receives as double-double pairs (hi, lo): over the pairs res =
+ * pred - obs, res^2, |res|, (pred + obs)^2, obs, pred, obs * pred; over the finite observations obs and obs^2; over the
+ * finite predictions pred and pred^2.  res and pred + obs are float64 operations on the widened inputs. */
+int psh_detcat_counts_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int obs_f64, int obs_shared, int K, size_t npix,
+                          const double *thr_fct_host, const double *thr_obs_host, int n_thresholds,
+                          unsigned long long *out_dev);
+int psh_detcont_sums_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int obs_f64, int obs_shared, int K, size_t npix,
+                         int conditioning, double thr_fct, double thr_obs, unsigned long long *counts_dev, double *sums_dev);
+
 /* ---- the DARTS motion estimate (csrc/darts.hip) ---------------------------------------------------------------- *
  * pysteps/motion/darts.py: the spectral band of the frames, the normal equations and the dense field; the small
  * solve stays on the host.  K_y = N_y + M_y, K_x = N_x + M_x; every call is queued on the library stream.

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dd.h"
 
 namespace psh {
 namespace {
@@ -28,65 +29,7 @@ constexpr int kMaxLevels = 16;
 // beside its spread (level 0 carries the masked field's mean), so the two sums are carried as unevaluated pairs
 // hi + lo (Knuth's two-sum, the product's error from an fma): ~106 bits, the cancellation then costs nothing
 // that shows in a double, and the order of the additions stops mattering at the 1e-16 level.  The kernel is
-// bound by the planes' bytes, the extra flops are free.
-struct dd {
-  double hi, lo;
-};
-
-__device__ __forceinline__ dd two_sum(double a, double b) {
-#pragma clang fp contract(off)
-  const double s = a + b;
-  const double bb = s - a;
-  const double e = (a - (s - bb)) + (b - bb);
-  return {s, e};
-}
-__device__ __forceinline__ dd quick_two_sum(double a, double b) {  // |a| >= |b|
-#pragma clang fp contract(off)
-  const double s = a + b;
-  return {s, b - (s - a)};
-}
-__device__ __forceinline__ dd dd_add_d(dd a, double b) {
-#pragma clang fp contract(off)
-  dd t = two_sum(a.hi, b);
-  t.lo = t.lo + a.lo;
-  return quick_two_sum(t.hi, t.lo);
-}
-__device__ __forceinline__ dd dd_add(dd a, dd b) {
-#pragma clang fp contract(off)
-  dd t = two_sum(a.hi, b.hi);
-  t.lo = t.lo + (a.lo + b.lo);
-  return quick_two_sum(t.hi, t.lo);
-}
-__device__ __forceinline__ dd dd_add_sq(dd a, double v) {  // a + v * v, the product exact
-#pragma clang fp contract(off)
-  const double p = v * v;
-  const double e = fma(v, v, -p);
-  dd t = two_sum(a.hi, p);
-  t.lo = t.lo + (a.lo + e);
-  return quick_two_sum(t.hi, t.lo);
-}
-__device__ __forceinline__ dd dd_div_d(dd a, double b) {
-#pragma clang fp contract(off)
-  const double q1 = a.hi / b;
-  const double r = fma(-q1, b, a.hi) + a.lo;
-  return quick_two_sum(q1, r / b);
-}
-__device__ __forceinline__ dd dd_sqr(dd a) {
-#pragma clang fp contract(off)
-  const double p = a.hi * a.hi;
-  const double e = fma(a.hi, a.hi, -p) + 2.0 * (a.hi * a.lo);
-  return quick_two_sum(p, e);
-}
-__device__ __forceinline__ dd dd_wave_sum(dd v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    dd o;
-    o.hi = __shfl_xor(v.hi, d);
-    o.lo = __shfl_xor(v.lo, d);
-    v = dd_add(v, o);
-  }
-  return v;
-}
+// bound by the planes' bytes, the extra flops are free.  The helpers are in dd.h.
 
 // one block's {sum, sum of squares} of a plane as four doubles
 struct Part {

@@ -259,6 +259,48 @@ def unpatch_fss():
     hip_mod._reference_fss_accum = None
 
 
+def patch_detscores():
+    """Replace ``det_cat_fct`` and ``det_cat_fct_accum`` of ``pysteps.verification.detcatscores`` and ``det_cont_fct`` and
+    ``det_cont_fct_accum`` of ``pysteps.verification.detcontscores`` by the device versions
+    (:mod:`pysteps_amd.verification.detcatscores`, :mod:`pysteps_amd.verification.detcontscores`).
+    ``pysteps.verification.interface.get_method`` imports the two ``_fct`` functions from their modules when it is
+    called (interface.py:167-168) and there is no table to add a name to, so the attributes are what has to change.
+    Inputs the device path declines, and the offline scores, run the reference's functions, which stay reachable."""
+    import pysteps.verification.detcatscores as ref_cat  # noqa: PLC0415
+    import pysteps.verification.detcontscores as ref_cont  # noqa: PLC0415
+
+    from .verification import detcatscores as hip_cat  # noqa: PLC0415
+    from .verification import detcontscores as hip_cont  # noqa: PLC0415
+
+    added = []
+    for ref_mod, hip_mod, stem in ((ref_cat, hip_cat, "det_cat_fct"), (ref_cont, hip_cont, "det_cont_fct")):
+        if getattr(ref_mod, stem + "_accum") is getattr(hip_mod, stem + "_accum"):
+            continue
+        for name, holder in ((stem, "_reference_fct"), (stem + "_accum", "_reference_fct_accum")):
+            setattr(ref_mod, "_reference_" + name, getattr(ref_mod, name))
+            setattr(hip_mod, holder, getattr(ref_mod, name))
+            setattr(ref_mod, name, getattr(hip_mod, name))
+            added.append("verification:" + name)
+    return added
+
+
+def unpatch_detscores():
+    """Undo :func:`patch_detscores`."""
+    import pysteps.verification.detcatscores as ref_cat  # noqa: PLC0415
+    import pysteps.verification.detcontscores as ref_cont  # noqa: PLC0415
+
+    from .verification import detcatscores as hip_cat  # noqa: PLC0415
+    from .verification import detcontscores as hip_cont  # noqa: PLC0415
+
+    for ref_mod, hip_mod, stem in ((ref_cat, hip_cat, "det_cat_fct"), (ref_cont, hip_cont, "det_cont_fct")):
+        for name in (stem, stem + "_accum"):
+            ref = getattr(ref_mod, "_reference_" + name, None)
+            if ref is not None:
+                setattr(ref_mod, name, ref)
+                delattr(ref_mod, "_reference_" + name)
+        hip_mod._reference_fct = hip_mod._reference_fct_accum = None
+
+
 def patch_noise_stddev_adj():
     """Replace ``pysteps.noise.utils.compute_noise_stddev_adjs`` by the device version
     (:mod:`pysteps_amd.noise.utils`).  ``nowcasts.steps`` with ``noise_stddev_adj="auto"`` looks the function up as
@@ -323,7 +365,7 @@ def register_postprocessing(override=False):
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
-             dilated_mask=False, fss=False, noise_stddev_adj=False):
+             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -340,7 +382,9 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     ``fss=True`` makes ``pysteps.verification`` count the fractions skill score on the device (:func:`patch_fss`;
     :func:`unpatch_fss` undoes it).  ``noise_stddev_adj=True`` makes ``nowcasts.steps(noise_stddev_adj="auto")``
     compute its adjustment coefficients on the device (:func:`patch_noise_stddev_adj`;
-    :func:`unpatch_noise_stddev_adj` undoes it)."""
+    :func:`unpatch_noise_stddev_adj` undoes it).  ``detscores=True`` makes ``pysteps.verification`` count contingency
+    tables and sum the continuous error moments on the device (:func:`patch_detscores`; :func:`unpatch_detscores`
+    undoes it)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -370,6 +414,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += patch_fss()
     if noise_stddev_adj:
         added += patch_noise_stddev_adj()
+    if detscores:
+        added += patch_detscores()
     if patch_main_loop:
         import importlib  # noqa: PLC0415
 
