@@ -404,6 +404,27 @@ int psh_detcat_counts_dev(const void *fct_dev, int fct_f64, const void *obs_dev,
 int psh_detcont_sums_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int obs_f64, int obs_shared, int K, size_t npix,
                          int conditioning, double thr_fct, double thr_obs, unsigned long long *counts_dev, double *sums_dev);
 
+/* ---- radially averaged power spectra (csrc/rapsd.hip) --------------------------------------------------------- *
+ * pysteps/utils/spectral.py:100-180 (rapsd) for a stack of K planes: the mean power over the coefficients of every
+ * integer radius r = round(sqrt(kx^2 + ky^2)) < nb, with l = max(m, n) and nb = l / 2 (+ 1 for odd l).  out_dev
+ * (K, nb) float64 receives the means, counts_dev (nb) the number of coefficients of every bin - a function of the shape,
+ * the same for both forms.  Sums are double-double, gathered bin by bin in a fixed order: the same bits in every run,
+ * for every K and at every position of a plane in the stack.  Queued on the library stream.
+ *  psh_rapsd_half_dev   K half spectra (K, m, n/2+1) complex128 as psh_fft_rfft2_dev writes them; the power is
+ *      |X|^2 / (m n), a column that has a mirror in the full plane counts twice.
+ *  psh_rapsd_full_dev   K shifted planes (K, m, n) of the power itself (the origin at [m/2, n/2]), float64 (f64) or
+ *      float32: rapsd's fft_method=None form.
+ *  psh_rapsd_counts_dev the counts alone: of the shifted plane (shifted != 0) or of the weighted half spectrum.
+ *  psh_rapsd_nonfinite_dev  counts_host[0] = NaN values, counts_host[1] = infinite values among `count` elements;
+ *      waits for the result.
+ *  psh_rapsd_fill_nan_dev   out (count) float64 = in widened, every NaN replaced by `fill` (what a caller does to a
+ *      nowcast member before it takes its spectrum). */
+int psh_rapsd_half_dev(const void *spec_dev, int K, int m, int n, double *out_dev, unsigned long long *counts_dev);
+int psh_rapsd_full_dev(const void *planes_dev, int f64, int K, int m, int n, double *out_dev, unsigned long long *counts_dev);
+int psh_rapsd_counts_dev(int m, int n, int shifted, unsigned long long *counts_dev);
+int psh_rapsd_nonfinite_dev(const void *in_dev, int f64, size_t count, unsigned long long *counts_host);
+int psh_rapsd_fill_nan_dev(const void *in_dev, int f64, size_t count, double fill, double *out_dev);
+
 /* ---- the DARTS motion estimate (csrc/darts.hip) ---------------------------------------------------------------- *
  * pysteps/motion/darts.py: the spectral band of the frames, the normal equations and the dense field; the small
  * solve stays on the host.  K_y = N_y + M_y, K_x = N_x + M_x; every call is queued on the library stream.

@@ -113,6 +113,11 @@ SIGNATURES = {
     "psh_detcat_counts_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
     "psh_detcont_sums_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_size_t, c_int, c_double, c_double, c_void_p,
                                      c_void_p]),
+    "psh_rapsd_half_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "psh_rapsd_full_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "psh_rapsd_counts_dev": (c_int, [c_int, c_int, c_int, c_void_p]),
+    "psh_rapsd_nonfinite_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
+    "psh_rapsd_fill_nan_dev": (c_int, [c_void_p, c_int, c_size_t, c_double, c_void_p]),
     "psh_darts_nonfinite_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     "psh_darts_band_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "psh_darts_gram_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p]),

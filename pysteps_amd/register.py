@@ -332,6 +332,38 @@ def unpatch_noise_stddev_adj():
     hip_mod._reference_fn = None
 
 
+def patch_rapsd():
+    """Replace ``pysteps.utils.spectral.rapsd`` by the device version (:mod:`pysteps_amd.utils.spectral`).
+    ``pysteps.utils.interface.get_method("rapsd")`` builds its table from ``spectral.rapsd`` when it is called and
+    ``noise.fftgenerators.initialize_param_2d_fft_filter`` calls ``utils.spectral.rapsd`` (fftgenerators.py:150), so both
+    go through the device after the swap; inputs the device path declines run the reference's function with a
+    ``RuntimeWarning``.  ``downscaling.rainfarm`` binds the name when it is imported (``from ..utils.spectral import
+    rapsd``) and keeps the reference's function."""
+    import pysteps.utils.spectral as ref_mod  # noqa: PLC0415
+
+    from .utils import spectral as hip_mod  # noqa: PLC0415
+
+    if ref_mod.rapsd is hip_mod.rapsd:
+        return []
+    ref_mod._reference_rapsd = ref_mod.rapsd
+    hip_mod._reference_rapsd = ref_mod.rapsd
+    ref_mod.rapsd = hip_mod.rapsd
+    return ["utils.spectral:rapsd"]
+
+
+def unpatch_rapsd():
+    """Undo :func:`patch_rapsd`."""
+    import pysteps.utils.spectral as ref_mod  # noqa: PLC0415
+
+    from .utils import spectral as hip_mod  # noqa: PLC0415
+
+    ref = getattr(ref_mod, "_reference_rapsd", None)
+    if ref is not None:
+        ref_mod.rapsd = ref
+        del ref_mod._reference_rapsd
+    hip_mod._reference_rapsd = None
+
+
 def register_nowcasts():
     """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) and ``"lagrangian_probability_hip"``
     (:func:`pysteps_amd.nowcasts.lagrangian_probability.forecast`) to pysteps' nowcast table
@@ -365,7 +397,7 @@ def register_postprocessing(override=False):
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
-             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False):
+             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False, rapsd=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -384,7 +416,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     compute its adjustment coefficients on the device (:func:`patch_noise_stddev_adj`;
     :func:`unpatch_noise_stddev_adj` undoes it).  ``detscores=True`` makes ``pysteps.verification`` count contingency
     tables and sum the continuous error moments on the device (:func:`patch_detscores`; :func:`unpatch_detscores`
-    undoes it)."""
+    undoes it).  ``rapsd=True`` makes ``pysteps.utils.spectral.rapsd`` bin its spectra on the device
+    (:func:`patch_rapsd`; :func:`unpatch_rapsd` undoes it)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -416,6 +449,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += patch_noise_stddev_adj()
     if detscores:
         added += patch_detscores()
+    if rapsd:
+        added += patch_rapsd()
     if patch_main_loop:
         import importlib  # noqa: PLC0415
 

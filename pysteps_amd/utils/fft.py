@@ -126,4 +126,5 @@ def get_hip(shape, fftn_shape=None, **kwargs):
     }
     if fftn_shape is not None:
         f["fftn"] = np.fft.fftn
+    f["pysteps_amd_hip"] = True  # marker: utils.spectral.rapsd takes its device path for this method object
     return SimpleNamespace(**f)
