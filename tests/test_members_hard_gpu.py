@@ -25,12 +25,11 @@ import pytest
 
 from conftest import nan_mismatch, rel_l2
 from helpers.bps import generate_bps
+from helpers.semilag_pointwise import EPS32, _disp_budget
 
 pytestmark = pytest.mark.gpu
 
 REL_L2_TOL = 1e-4  # the contract (BASELINE.json north_star)
-DISP_TOL = 1e-4
-EPS32 = 2.0**-24  # unit roundoff of float32
 ROUTES = ("pair", "single", "unpacked", "f64")
 NAN_EDGE = 2  # NaN-mask pixels a plane may differ by (test_ensemble_gpu.py: an edge crossed at an exact integer)
 _SAMPLE_ULPS = 8  # (b): bilinear blend in float32, see _check_call
@@ -168,24 +167,6 @@ class _Oracle:
 
 
 # ---- error budget ------------------------------------------------------------------------------------------------------
-def _disp_budget(vmax, lip, smax, n_sub):
-    """Largest trajectory difference float32 split arithmetic may leave after ``n_sub`` sub-steps.
-
-    Per sub-step the kernel rounds: the bilinear velocity samples (weights 1 - f and their products, three fma's: <= 6
-    roundings of at most |V|), the perturbation a V_par + b V_perp (a, b and V_par rounded to float32: <= 4 roundings of
-    |V|), the scaling by the step (1), and the two retreats f - w (1/2 ulp of |f - w| <= |V| s + 1 each).  Two velocity
-    samples per sub-step: e1 <= 2 * (6 + 4 + 1 + 1) * u * max(|V| s, 1) < 24 u max(|V| s, 1), u = 2^-24.  An error
-    already made is carried on and changes the next velocity sample by at most lip * error (lip = the largest
-    difference of neighbouring velocity values, the Lipschitz constant of the bilinear interpolant), i.e. it grows by
-    (1 + lip s) per sub-step; after N sub-steps: N e1 (1 + lip s)^N.  Capped by the contract.  A calm pixel in a
-    moving flow or a sentinel patch is a jump of |V| between neighbours: a trajectory that samples it amplifies what it
-    carries by up to (1 + |V| s) per pass (6e-4 px was seen after three calls at 29 px / step), so such trajectories
-    (``touched``) are held to (b) and to the sentinel rules only, and lip is taken without those pixels."""
-    e1 = 24.0 * EPS32 * max(vmax * smax, 1.0)
-    grow = (1.0 + lip * smax) ** n_sub
-    return min(n_sub * e1 * grow, DISP_TOL)
-
-
 def _field_budget(member, disp_bar):
     """rel-L2 a plane may differ from the oracle's: a position error <= d moves a bilinear sample by at most
     d (|dp/dx| + |dp/dy|) of its cell, so the L2 norm of the difference is at most d ||grad||_2 (neighbour differences
