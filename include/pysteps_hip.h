@@ -40,7 +40,20 @@ extern "C" {
 #define PSH_EINPUT (-7)   /* input values the reference rejects (non-finite fields); see psh_semilag_host */
 
 /* ---- runtime ----------------------------------------------------------- */
-int psh_init(int device_id);          /* idempotent; binds the calling process to one GPU */
+/* psh_init binds the calling process to one GPU (device_id < 0: device 0); idempotent while bound.
+ *
+ * psh_shutdown ends the binding and releases everything the library owns: its streams and events, the device and
+ * pinned blocks it keeps for itself (scratch and staging slots, the window kernel's tile-order tables, the
+ * Lucas-Kanade workspace, corner requests still in flight, FFT tables, the mask word), the blocks cached by psh_free /
+ * psh_host_free, every block from psh_malloc / psh_host_alloc that is still handed out, and a communicator left open
+ * (as psh_comm_destroy).  It waits for the queued work first.  Afterwards every device pointer, pinned pointer and
+ * event the library ever handed out is invalid and must not be used; psh_free(p) and psh_host_free(p) of such a pointer
+ * return PSH_OK while the library is unbound and PSH_EINVAL (unknown pointer, nothing freed) after the next psh_init -
+ * drop the pointers before that psh_init, since a new block may reuse an old address.
+ * Caller-owned handles are NOT released: destroy them BEFORE psh_shutdown - generator handles (psh_rng_destroy),
+ * Lucas-Kanade pyramid handles (psh_lk_pyramids_free), probability-matching plans (psh_probmatch_plan_destroy) and
+ * events (psh_event_destroy).  psh_init may then bind any device, the same or another. */
+int psh_init(int device_id);
 int psh_shutdown(void);
 const char *psh_last_error(void);
 const char *psh_version(void);

@@ -175,3 +175,6 @@ int psh_comm_destroy(void) {
 }
 
 }  // extern "C"
+
+// psh_shutdown closes a communicator that is still open, by the same path
+[[maybe_unused]] static const int g_comm_hook = psh::at_shutdown([] { (void)psh_comm_destroy(); });

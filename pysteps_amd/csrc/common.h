@@ -36,22 +36,27 @@ struct Context {
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
   // small persistent device scratch (per-step scale factors etc.)
   void *scratch = nullptr;
-  size_t scratch_bytes = 0;
   // "a wet pixel was seen" word of psh_steps_incremental_mask_dev and the generation number its launches stamp it with
   int *mask_any = nullptr;
   int mask_generation = 0;
-  // pinned staging buffer for pageable host copies
+  // pinned half of the const_slot ring and the slot it hands out next
   void *pinned = nullptr;
-  size_t pinned_bytes = 0;
+  size_t const_next = 0;
   std::recursive_mutex mu;
 };
 
 Context &ctx();
 int fail(int code, const char *fmt, ...);
 int ensure_scratch(size_t nbytes);
-// Small pinned host blocks that live as long as the library (staging slots of single translation
-// units): allocated on first use, released by psh_shutdown.  *slot stays NULL on failure.
+// Ownership rule (registry.h): every device or pinned block the library keeps for itself hangs on a slot and comes from
+// these - allocated on first use, regrown (waits for the library stream, contents not kept) when more is asked for,
+// freed with NULL written to *slot by psh_shutdown.  *slot stays NULL on failure.  Lock held.
+int persistent_device(void **slot, size_t nbytes);
 int persistent_pinned(void **slot, size_t nbytes);
+template <class T> int persistent_device(T **slot, size_t n) { return persistent_device(reinterpret_cast<void **>(slot), n); }
+void persistent_free(void **slot);            // one block, now: a table whose upload failed
+unsigned long long persistent_generation();   // moves with every allocation / release above: guards pointers INTO blocks
+int at_shutdown(void (*hook)());  // streams, events, pools, ring positions: runs in every psh_shutdown after the blocks are gone
 // Fork: *side will run after everything queued on the main stream so far.  Join: the main stream
 // continues after everything queued on the side stream.  Lock held by the caller.  Blocks handed
 // out by psh_malloc are ordered on the MAIN stream: a block used on the side stream has to be
@@ -99,7 +104,7 @@ hipError_t launch_convert_f32_f64(const float *in, double *out, size_t n, hipStr
 // pinned host blocks, cached like the device blocks; PSH_ENOMEM beyond PYSTEPS_HIP_PINNED_BYTES
 int pinned_alloc(void **host_ptr, size_t nbytes);
 int pinned_free(void *host_ptr);
-void pinned_release_cache();
+void pinned_release_cache(bool live = false);  // live: also the blocks still handed out (psh_shutdown)
 
 // ---- kernel launchers (one per .hip translation unit) ----------------------
 struct SemilagArgs {
@@ -148,7 +153,6 @@ struct IdwDyn {
 
 // ---- FFTs (fft.hip) -----------------------------------------------------------
 bool fft_shape_supported(int m, int n);
-void fft_release();  // frees the twiddle tables (psh_shutdown)
 int fft_irfft2_weighted(const void *spec_dev, const double *weights_dev, int m, int n, double *out_dev,
                         void *scratch_dev, unsigned long long *min_key_dev = nullptr);
 

@@ -522,17 +522,12 @@ int ilog2_exact(int v) {
   return l;
 }
 
-// twiddle table of a length, device resident, computed once (lock held by the callers)
-std::map<int, double2 *> &twiddle_cache() {
-  static std::map<int, double2 *> cache;
-  return cache;
-}
-
+// twiddle table of a length (lock held); the map's values are registered slots: NULL again after psh_shutdown, never erased
 int twiddles(int n, const double2 **tw_out) {
-  std::map<int, double2 *> &cache = twiddle_cache();
-  auto it = cache.find(n);
-  if (it != cache.end()) {
-    *tw_out = it->second;
+  static std::map<int, double2 *> cache;
+  double2 *&dev = cache[n];
+  if (dev != nullptr) {
+    *tw_out = dev;
     return PSH_OK;
   }
   const int count = n / 2 > 0 ? n / 2 : 1;
@@ -542,15 +537,13 @@ int twiddles(int n, const double2 **tw_out) {
     const long double a = step * static_cast<long double>(k);
     host[k] = make_double2(static_cast<double>(cosl(a)), static_cast<double>(sinl(a)));
   }
-  void *dev = nullptr;
-  PSH_HIP(hipMalloc(&dev, host.size() * sizeof(double2)));
+  if (int rc = persistent_device(&dev, host.size() * sizeof(double2))) return rc;
   const hipError_t e = hipMemcpy(dev, host.data(), host.size() * sizeof(double2), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    (void)hipFree(dev);
+    persistent_free(reinterpret_cast<void **>(&dev));
     return fail(PSH_EHIP, "fft: twiddle upload failed: %s", hipGetErrorString(e));
   }
-  cache[n] = static_cast<double2 *>(dev);
-  *tw_out = cache[n];
+  *tw_out = dev;
   return PSH_OK;
 }
 
@@ -566,12 +559,8 @@ constexpr int kBluesteinMax = 1 << (kFftMaxLog - 1);  // 2 n - 1 <= 8192
 
 // chirp b_j = exp(i pi j^2 / n) and the spectrum of its symmetric extension, per length
 struct ChirpTables {
-  double2 *chirp, *filter;
+  double2 *chirp = nullptr, *filter = nullptr;  // registered slots, as the twiddle tables
 };
-std::map<int, ChirpTables> &chirp_cache() {
-  static std::map<int, ChirpTables> cache;
-  return cache;
-}
 
 // the 1-D transform of one axis (lock held by the callers)
 int make_dft(const char *who, int n, Dft *d) {
@@ -590,9 +579,9 @@ int make_dft(const char *who, int n, Dft *d) {
   const int M = 1 << logm;
   d->logm = logm;
   if (int rc = twiddles(M, &d->tw)) return rc;
-  std::map<int, ChirpTables> &cache = chirp_cache();
-  auto it = cache.find(n);
-  if (it == cache.end()) {
+  static std::map<int, ChirpTables> cache;
+  ChirpTables &t = cache[n];
+  if (t.chirp == nullptr || t.filter == nullptr) {
     // j^2 is reduced modulo 2 n exactly before the angle is formed: b_j has period 2 n in j^2
     std::vector<double2> b(static_cast<size_t>(n)), ext(static_cast<size_t>(M), make_double2(0.0, 0.0));
     const long double pi = 3.14159265358979323846264338327950288L;
@@ -603,23 +592,29 @@ int make_dft(const char *who, int n, Dft *d) {
       ext[j] = b[j];
       if (j) ext[M - j] = b[j];
     }
-    ChirpTables t{nullptr, nullptr};
-    PSH_HIP(hipMalloc(reinterpret_cast<void **>(&t.chirp), b.size() * sizeof(double2)));
-    PSH_HIP(hipMalloc(reinterpret_cast<void **>(&t.filter), ext.size() * sizeof(double2)));
-    PSH_HIP(hipMemcpy(t.chirp, b.data(), b.size() * sizeof(double2), hipMemcpyHostToDevice));
-    PSH_HIP(hipMemcpy(t.filter, ext.data(), ext.size() * sizeof(double2), hipMemcpyHostToDevice));
-    // its spectrum: one plain row transform of length M, in place
-    Dft plain{M, logm, d->tw, nullptr, nullptr};
-    const size_t lds = static_cast<size_t>(lds_elems(M)) * sizeof(double2);
-    if (int rc = allow_lds(fft_rows_c2c<false>, lds)) return rc;
-    hipStream_t stream = ctx().stream;
-    hipLaunchKernelGGL(fft_rows_c2c<false>, dim3(1), dim3(fft_threads(M)), lds, stream, t.filter, plain, t.filter);
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipStreamSynchronize(stream));
-    it = cache.emplace(n, t).first;
+    auto fill = [&]() -> int {
+      if (int rc = persistent_device(&t.chirp, b.size() * sizeof(double2))) return rc;
+      if (int rc = persistent_device(&t.filter, ext.size() * sizeof(double2))) return rc;
+      PSH_HIP(hipMemcpy(t.chirp, b.data(), b.size() * sizeof(double2), hipMemcpyHostToDevice));
+      PSH_HIP(hipMemcpy(t.filter, ext.data(), ext.size() * sizeof(double2), hipMemcpyHostToDevice));
+      // its spectrum: one plain row transform of length M, in place
+      Dft plain{M, logm, d->tw, nullptr, nullptr};
+      const size_t lds = static_cast<size_t>(lds_elems(M)) * sizeof(double2);
+      if (int rc = allow_lds(fft_rows_c2c<false>, lds)) return rc;
+      hipStream_t stream = ctx().stream;
+      hipLaunchKernelGGL(fft_rows_c2c<false>, dim3(1), dim3(fft_threads(M)), lds, stream, t.filter, plain, t.filter);
+      PSH_HIP(hipGetLastError());
+      PSH_HIP(hipStreamSynchronize(stream));
+      return PSH_OK;
+    };
+    if (int rc = fill()) {  // half-made tables must not pass for a hit (the stream is idle or never saw them)
+      persistent_free(reinterpret_cast<void **>(&t.chirp));
+      persistent_free(reinterpret_cast<void **>(&t.filter));
+      return rc;
+    }
   }
-  d->chirp = it->second.chirp;
-  d->filter = it->second.filter;
+  d->chirp = t.chirp;
+  d->filter = t.filter;
   return PSH_OK;
 }
 
@@ -715,18 +710,6 @@ extern "C" int psh_fft_rfft2_dev(const double *in_dev, int m, int n, void *out_d
   PSH_HIP(hipGetLastError());
   return psh::launch_cols(false, out, cols, n / 2 + 1, 1.0, out, c.stream);
 }
-
-namespace psh {
-void fft_release() {  // psh_shutdown: the tables belong to the device that is being released
-  for (auto &kv : twiddle_cache()) (void)hipFree(kv.second);
-  twiddle_cache().clear();
-  for (auto &kv : chirp_cache()) {
-    (void)hipFree(kv.second.chirp);
-    (void)hipFree(kv.second.filter);
-  }
-  chirp_cache().clear();
-}
-}  // namespace psh
 
 // irfft2(spectrum * weights) -> real (m, n); weights (m, n/2+1) float64 or nullptr; the spectrum is
 // left untouched (the column pass writes into `scratch`, (m, n/2+1) complex128).  Lock held.

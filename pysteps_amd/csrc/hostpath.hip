@@ -217,18 +217,24 @@ int pinned_free(void *host_ptr) {
   return PSH_OK;
 }
 
-void pinned_release_cache() {
+void pinned_release_cache(bool live) {
   PinnedPool &p = pool();
   std::lock_guard<std::mutex> g(p.mu);
   for (auto &kv : p.free_blocks)
     for (void *q : kv.second) (void)hipHostFree(q);
   p.free_blocks.clear();
   p.cached = 0;
-  if (g_down_stream) {
-    (void)hipStreamDestroy(g_down_stream);
-    g_down_stream = nullptr;
-  }
+  if (!live) return;
+  for (auto &kv : p.live) (void)hipHostFree(kv.first);
+  p.live.clear();
+  p.in_use = 0;
 }
+
+[[maybe_unused]] static const int g_hostpath_hook = at_shutdown([] {  // the download stream and every pinned block
+  if (g_down_stream) (void)hipStreamDestroy(g_down_stream);
+  g_down_stream = nullptr;
+  pinned_release_cache(true);
+});
 
 }  // namespace psh
 

@@ -1949,27 +1949,12 @@ void launch_lk_response(dim3 grid, hipStream_t stream, int block_size, const uns
 #undef PSH_CRN_LAUNCH
 }
 
+// the frame workspace: one registered block that grows to the largest frame seen
 static int ensure_lk_ws(size_t nbytes, void **ptr) {
-  Context &c = ctx();
   static void *ws = nullptr;
-  static size_t ws_bytes = 0;
-  if (ws_bytes < nbytes) {
-    if (ws) {
-      PSH_HIP(hipStreamSynchronize(c.stream));
-      PSH_HIP(hipFree(ws));
-      ws = nullptr;
-      ws_bytes = 0;
-    }
-    hipError_t e = hipMalloc(&ws, nbytes);
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      return fail(PSH_ENOMEM, "LK workspace of %zu bytes does not fit in device memory", nbytes);
-    }
-    PSH_HIP(e);
-    ws_bytes = nbytes;
-  }
+  const int rc = persistent_device(&ws, nbytes);
   *ptr = ws;
-  return PSH_OK;
+  return rc;
 }
 
 // the three frame passes (cleaning, opening, uint8 renderings) of one frame on `stream` with the
@@ -2441,18 +2426,7 @@ int psh_lk_corners_launch_dev(const unsigned char *feature_u8_dev, const float *
   if (!job.ready) PSH_HIP(hipEventCreateWithFlags(&job.ready, hipEventDisableTiming));
   const bool host_ordered = !psh::corner_order_supported(m, n, min_distance, max_corners);
   const size_t pin_need = kPinnedHeader + (host_ordered ? 0 : static_cast<size_t>(max_corners) * sizeof(float2));
-  static size_t pin_have[kMaxCornerJobs] = {0};
-  const int slot = static_cast<int>(&job - g_corner_jobs);
-  if (pin_have[slot] < pin_need) {
-    if (job.pinned) {
-      PSH_HIP(hipStreamSynchronize(c.stream));
-      PSH_HIP(hipHostFree(job.pinned));
-      job.pinned = nullptr;
-      pin_have[slot] = 0;
-    }
-    PSH_HIP(hipHostMalloc(&job.pinned, pin_need, hipHostMallocDefault));
-    pin_have[slot] = pin_need;
-  }
+  if (int rc = psh::persistent_pinned(&job.pinned, pin_need)) return rc;
   char *pin = static_cast<char *>(job.pinned);
   const CornerWs w(m, n, block_size);
   void *ws = nullptr;
@@ -2570,20 +2544,14 @@ int psh_lk_greedy_host(const unsigned long long *keys, int count, int m, int n, 
 
 extern "C++" {
 namespace psh {
-// drop every request still in flight (after an error between launch and finish)
-void lk_corners_drain() {
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  while (g_corner_count > 0) {
-    CornerJob &job = g_corner_jobs[g_corner_head];
-    g_corner_head = (g_corner_head + 1) % kMaxCornerJobs;
-    --g_corner_count;
-    job.active = false;
-    if (job.ready) (void)hipEventSynchronize(job.ready);
-    if (job.ws) (void)psh_free(job.ws);
-    job.ws = nullptr;
+// psh_shutdown: every request still in flight is dropped; its pinned block and device block went with the rest
+[[maybe_unused]] static const int g_corner_jobs_hook = at_shutdown([] {
+  for (CornerJob &job : g_corner_jobs) {
+    if (job.ready) (void)hipEventDestroy(job.ready);
+    job = CornerJob{};
   }
-}
+  g_corner_head = g_corner_count = 0;
+});
 int lk_corners_in_flight_limit() { return kMaxCornerJobs; }
 }  // namespace psh
 }  // extern "C++"

@@ -406,7 +406,7 @@ extern "C" int psh_steps_incremental_mask_dev(const double *field_dev, int m, in
   const size_t bit_bytes = static_cast<size_t>(m) * words_per_row * sizeof(unsigned long long);
   // the "anything wet" word and its generation counter (see wet_bits)
   if (!c.mask_any) {
-    PSH_HIP(hipMalloc(reinterpret_cast<void **>(&c.mask_any), sizeof(int)));
+    if (int rc = psh::persistent_device(&c.mask_any, sizeof(int))) return rc;
     PSH_HIP(hipMemsetAsync(c.mask_any, 0, sizeof(int), c.stream));  // once, in stream order
     c.mask_generation = 0;
   }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "registry.h"
 
 namespace psh {
 
@@ -25,25 +26,31 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
-// generation of the scratch allocation: whoever remembers a pointer into it (the step factors of the last
-// extrapolation) compares generations, not addresses - a new block can land where the old one was
-static unsigned long long g_scratch_generation = 1;
-
-int ensure_scratch(size_t nbytes) {
-  Context &c = ctx();
-  if (c.scratch_bytes >= nbytes) return PSH_OK;
-  ++g_scratch_generation;
-  if (c.scratch) {
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    PSH_HIP(hipFree(c.scratch));
-    c.scratch = nullptr;
-    c.scratch_bytes = 0;
+// ---- the registry of everything the library owns (registry.h) with HIP underneath ------------------
+static int registry_alloc(MemKind kind, void **out, size_t nbytes) {
+  void *p = nullptr;
+  const hipError_t e = kind == kMemPinned ? hipHostMalloc(&p, nbytes, hipHostMallocDefault) : hipMalloc(&p, nbytes);
+  if (e == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(PSH_ENOMEM, "a library-owned block of %zu bytes does not fit in memory (kind %d)", nbytes, kind);
   }
-  size_t want = nbytes < 65536 ? 65536 : nbytes;
-  PSH_HIP(hipMalloc(&c.scratch, want));
-  c.scratch_bytes = want;
+  PSH_HIP(e);
+  *out = p;
   return PSH_OK;
 }
+static void registry_release(MemKind kind, void *block) { (void)(kind == kMemPinned ? hipHostFree(block) : hipFree(block)); }
+static int registry_quiesce() { return psh_sync(); }
+static Registry &registry() {
+  static Registry r{registry_alloc, registry_release, registry_quiesce};
+  return r;
+}
+
+int persistent_device(void **slot, size_t nbytes) { return registry().ensure(kMemDevice, slot, nbytes); }
+int persistent_pinned(void **slot, size_t nbytes) { return registry().ensure(kMemPinned, slot, nbytes); }
+void persistent_free(void **slot) { registry().drop(slot); }
+unsigned long long persistent_generation() { return registry().generation; }
+int at_shutdown(void (*hook)()) { return registry().hooks.push_back(hook), 0; }
+int ensure_scratch(size_t nbytes) { return persistent_device(&ctx().scratch, nbytes < 65536 ? 65536 : nbytes); }
 
 // ---- stream-ordered caching allocator ---------------------------------------
 // Every kernel and copy of the library is ordered on ONE stream, so a block handed
@@ -68,27 +75,17 @@ static BlockCache &cache() {
   return c;
 }
 
-static void release_cache() {
+static void release_cache(bool live = false) {  // live: also the blocks still handed out (psh_shutdown)
   BlockCache &bc = cache();
   for (auto &kv : bc.free_blocks)
     for (void *p : kv.second) (void)hipFree(p);
   bc.free_blocks.clear();
   bc.cached_bytes = 0;
+  if (!live) return;
+  for (auto &kv : bc.live) (void)hipFree(kv.first);
+  bc.live.clear();
 }
-
-static int ensure_pinned(size_t nbytes) {
-  Context &c = ctx();
-  if (c.pinned_bytes >= nbytes) return PSH_OK;
-  if (c.pinned) {
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    PSH_HIP(hipHostFree(c.pinned));
-    c.pinned = nullptr;
-    c.pinned_bytes = 0;
-  }
-  PSH_HIP(hipHostMalloc(&c.pinned, nbytes, hipHostMallocDefault));
-  c.pinned_bytes = nbytes;
-  return PSH_OK;
-}
+[[maybe_unused]] static const int g_blocks_hook = at_shutdown([] { release_cache(true); });
 
 // A fresh 4 KiB pinned slot + its device twin per call, so that back-to-back asynchronous calls
 // never overwrite constants a queued kernel still has to read; the ring synchronises with the
@@ -97,11 +94,11 @@ constexpr size_t kConstSlots = 64;
 
 int const_slot(float **host, const float **dev) {
   Context &c = ctx();
-  static size_t slot = 0;
+  size_t &slot = c.const_next;
   const size_t n_slots = kConstSlots;
   // one more device slot than the ring hands out: the extrapolator's private one (semilag_factor_slot)
   if (int rc = ensure_scratch((n_slots + 1) * kConstSlotFloats * sizeof(float))) return rc;
-  if (int rc = ensure_pinned(n_slots * kConstSlotFloats * sizeof(float))) return rc;
+  if (int rc = persistent_pinned(&c.pinned, n_slots * kConstSlotFloats * sizeof(float))) return rc;
   if (slot == n_slots) {  // ring wrapped: make sure the oldest slots are consumed
     PSH_HIP(hipStreamSynchronize(c.stream));
     slot = 0;
@@ -114,7 +111,7 @@ int const_slot(float **host, const float **dev) {
 
 // The device slot behind the ring: only the extrapolator writes it (its per-step scale factors, kept from
 // call to call while they do not change).  No ring user can overwrite it however many slots are taken in
-// between; it moves only when the scratch block is reallocated (g_scratch_generation).
+// between; it moves only when the scratch block is reallocated (persistent_generation).
 static int semilag_factor_slot(const float **dev) {
   if (int rc = ensure_scratch((kConstSlots + 1) * kConstSlotFloats * sizeof(float))) return rc;
   *dev = static_cast<float *>(ctx().scratch) + kConstSlots * kConstSlotFloats;
@@ -175,31 +172,6 @@ int psh_init(int device_id) {
 
 extern "C++" {
 namespace psh {
-namespace {
-struct PinnedSlot {
-  void **slot;
-};
-std::vector<PinnedSlot> &pinned_slots() {
-  static std::vector<PinnedSlot> v;
-  return v;
-}
-}  // namespace
-
-int persistent_pinned(void **slot, size_t nbytes) {
-  if (*slot) return PSH_OK;
-  PSH_HIP(hipHostMalloc(slot, nbytes, hipHostMallocDefault));
-  pinned_slots().push_back(PinnedSlot{slot});
-  return PSH_OK;
-}
-
-static void release_persistent_pinned() {
-  for (PinnedSlot &p : pinned_slots()) {
-    if (*p.slot) (void)hipHostFree(*p.slot);
-    *p.slot = nullptr;
-  }
-  pinned_slots().clear();
-}
-
 int side_begin(hipStream_t *side) {
   Context &c = ctx();
   if (!c.side) {
@@ -219,6 +191,15 @@ int side_end() {
   PSH_HIP(hipStreamWaitEvent(c.stream, c.join_ev, 0));
   return PSH_OK;
 }
+[[maybe_unused]] static const int g_side_hook = at_shutdown([] {
+  Context &c = ctx();
+  if (!c.side) return;
+  (void)hipStreamDestroy(c.side);
+  (void)hipEventDestroy(c.fork_ev);
+  (void)hipEventDestroy(c.join_ev);
+  c.side = nullptr;
+  c.fork_ev = c.join_ev = nullptr;
+});
 }  // namespace psh
 }  // extern "C++"
 
@@ -226,28 +207,14 @@ int psh_shutdown(void) {
   psh::Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   if (!c.ready) return PSH_OK;
+  (void)hipSetDevice(c.device);
   (void)hipStreamSynchronize(c.stream);
-  psh::release_cache();
-  psh::pinned_release_cache();
-  psh::release_persistent_pinned();
-  psh::fft_release();
-  if (c.scratch) (void)hipFree(c.scratch);
-  if (c.mask_any) (void)hipFree(c.mask_any);
-  c.mask_any = nullptr;
-  ++psh::g_scratch_generation;
-  if (c.pinned) (void)hipHostFree(c.pinned);
+  if (c.side) (void)hipStreamSynchronize(c.side);
+  psh::registry().release_all();  // every registered block, then every translation unit's hook
   (void)hipStreamDestroy(c.stream);
-  if (c.side) {
-    (void)hipStreamSynchronize(c.side);
-    (void)hipStreamDestroy(c.side);
-    (void)hipEventDestroy(c.fork_ev);
-    (void)hipEventDestroy(c.join_ev);
-    c.side = nullptr;
-    c.fork_ev = c.join_ev = nullptr;
-  }
-  c.scratch = c.pinned = nullptr;
-  c.scratch_bytes = c.pinned_bytes = 0;
   c.stream = nullptr;
+  c.const_next = 0;
+  c.mask_generation = 0;
   c.ready = false;
   return PSH_OK;
 }
@@ -353,8 +320,7 @@ int psh_malloc(void **dev_ptr, size_t nbytes) {
 }
 
 int psh_free(void *dev_ptr) {
-  PSH_REQUIRE_INIT();
-  if (!dev_ptr) return PSH_OK;
+  if (!ctx().ready || !dev_ptr) return PSH_OK;  // after psh_shutdown the block is gone already
   psh::Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
@@ -539,12 +505,12 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
   // kernel that read the old factors was queued before the copy.
   static std::vector<float> last_scales;
   static const float *last_dev = nullptr;
-  static unsigned long long last_generation = 0;
+  static unsigned long long last_generation = 0;  // persistent_generation() when last_dev was taken
   const double sub = n_iter > 1 ? static_cast<double>(n_iter) : 1.0;
   std::vector<float> scales(static_cast<size_t>(T));
   for (int t = 0; t < T; ++t) scales[static_cast<size_t>(t)] = static_cast<float>(steps_host[t] / sub);
   const float *d = nullptr;
-  if (last_dev != nullptr && last_generation == psh::g_scratch_generation && scales.size() == last_scales.size() &&
+  if (last_dev != nullptr && last_generation == psh::persistent_generation() && scales.size() == last_scales.size() &&
       std::memcmp(scales.data(), last_scales.data(), scales.size() * sizeof(float)) == 0) {
     d = last_dev;
   } else {
@@ -556,7 +522,7 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
     PSH_HIP(hipMemcpyAsync(const_cast<float *>(d), h, T * sizeof(float), hipMemcpyHostToDevice, c.stream));
     last_scales = scales;
     last_dev = d;
-    last_generation = psh::g_scratch_generation;
+    last_generation = psh::persistent_generation();
   }
 
   psh::SemilagArgs a;

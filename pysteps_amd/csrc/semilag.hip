@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -1313,15 +1314,18 @@ bool semilag_window_eligible(const SemilagArgs &a) {
 
 // ---- the order the tiles are started in (see win_next_slot) ----------------------------------------------
 // One table per tile grid, built on the host and kept on the device.  Slot s belongs to XCD s % 8.
+// dev, stage, g_win_queue, g_win_stats: registered blocks, NULL again after psh_shutdown (a miss for the lookup below)
 struct WinOrder {
   int tiles_x = 0, tiles_y = 0, tile_h = 0, mode = -1;
   int *dev = nullptr;
+  void *stage = nullptr;  // pinned source of the upload of a table too long for one const_slot
 };
 static WinOrder g_win_orders[8];
 static int g_win_orders_next = 0;
 static unsigned *g_win_queue = nullptr;  // kQueueRing x 16 words: the cursors of persistent launches
 static unsigned g_win_queue_turn = 0;
 constexpr int kQueueRing = 16;
+[[maybe_unused]] static const int g_win_hook = at_shutdown([] { g_win_orders_next = g_win_queue_turn = 0; });
 
 // mode bit 0: XCD cells (else one band of tiles per XCD), bit 1: border rings first
 static std::vector<int> win_order_table(int tiles_x, int tiles_y, int tile_h, int mode) {
@@ -1362,15 +1366,20 @@ static const int *win_order(int tiles_x, int tiles_y, int tile_h, int mode, hipS
   WinOrder &o = g_win_orders[g_win_orders_next];
   g_win_orders_next = (g_win_orders_next + 1) % 8;
   const std::vector<int> table = win_order_table(tiles_x, tiles_y, tile_h, mode);
-  if (o.dev != nullptr) {
-    (void)hipStreamSynchronize(stream);  // a launch in flight may still read the table this slot held
-    (void)hipFree(o.dev);
-    o.dev = nullptr;
+  const size_t bytes = table.size() * sizeof(int);  // eviction: a launch in flight may still read the old table
+  if (o.dev != nullptr && hipStreamSynchronize(stream) != hipSuccess) return nullptr;
+  float *src = nullptr;
+  const float *ring_dev = nullptr;  // only the pinned half of a ring slot is used (staging)
+  if (bytes > kConstSlotFloats * sizeof(float)) {
+    if (persistent_pinned(&o.stage, bytes) != PSH_OK) return nullptr;
+    src = static_cast<float *>(o.stage);
+  } else if (const_slot(&src, &ring_dev) != PSH_OK) {
+    return nullptr;
   }
-  if (hipMalloc(&o.dev, table.size() * sizeof(int)) != hipSuccess) return nullptr;
-  if (hipMemcpy(o.dev, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(o.dev);
-    o.dev = nullptr;
+  std::memcpy(src, table.data(), bytes);
+  if (persistent_device(&o.dev, bytes) != PSH_OK) return nullptr;
+  if (hipMemcpyAsync(o.dev, src, bytes, hipMemcpyHostToDevice, stream) != hipSuccess) {
+    persistent_free(reinterpret_cast<void **>(&o.dev));
     return nullptr;
   }
   o.tiles_x = tiles_x;
@@ -1408,15 +1417,15 @@ static hipError_t launch_window(const SemilagArgs &a, hipStream_t stream) {
   int grid_x = tiles_per_xcd * kNumXcd;
   if (persist && (grid_x > resident || persist > 1)) {
     if (g_win_queue == nullptr) {
-      if (hipMalloc(&g_win_queue, kQueueRing * 16 * sizeof(unsigned)) != hipSuccess) return hipErrorOutOfMemory;
-      if (hipMemset(g_win_queue, 0, kQueueRing * 16 * sizeof(unsigned)) != hipSuccess) return hipErrorUnknown;
+      if (persistent_device(&g_win_queue, kQueueRing * 16 * sizeof(unsigned)) != PSH_OK) return hipErrorOutOfMemory;
+      if (hipMemsetAsync(g_win_queue, 0, kQueueRing * 16 * sizeof(unsigned), stream) != hipSuccess) return hipErrorUnknown;
     }
     queue = g_win_queue + 16 * (g_win_queue_turn++ % kQueueRing);
     grid_x = resident;
   }
   const dim3 grid(grid_x), block(C::kThreads);
   if (want_stats) {
-    if (g_win_stats == nullptr && hipMalloc(&g_win_stats, 4 * sizeof(unsigned long long)) != hipSuccess) g_win_stats = nullptr;
+    (void)persistent_device(&g_win_stats, 4 * sizeof(unsigned long long));  // stays NULL on failure
     if (g_win_stats != nullptr) (void)hipMemsetAsync(g_win_stats, 0, 4 * sizeof(unsigned long long), stream);
   }
 #define PSH_WIN_LAUNCH(GEN, PERSIST)                                                                               \
