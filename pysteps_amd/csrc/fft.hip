@@ -63,11 +63,13 @@ __device__ __forceinline__ double2 cmul(double2 a, double2 w) {
   return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
 }
 
-// one butterfly of a pass (two radix-2 layers): wb = W_4h^j (already conjugated for INV); the results
-// replace x0..x3 at the positions they were read from (e0, e0 + h, e0 + 2h, e0 + 3h)
+// one butterfly of a pass (two radix-2 layers): wb = W_4h^j, wa = W_2h^j (already conjugated for INV); the results
+// replace x0..x3 at the positions they were read from (e0, e0 + h, e0 + 2h, e0 + 3h).  wa comes from the table like wb:
+// formed in flight as wb * wb it is 1.5 eps off instead of 0.5, the same way in every butterfly of a layer, and a tone
+// adds that up coherently - the bin of the tone (1, 1) of a 64 x 128 rfft2 was 250 u off against 28 u with the table
+// entry (u = 2^-53 rms of the spectrum; tests/test_fft_pointwise_gpu.py).
 template <bool INV>
-__device__ __forceinline__ void radix4(double2 &x0, double2 &x1, double2 &x2, double2 &x3, double2 wb) {
-  const double2 wa = cmul(wb, wb);                                                  // W_2h^j
+__device__ __forceinline__ void radix4(double2 &x0, double2 &x1, double2 &x2, double2 &x3, double2 wb, double2 wa) {
   const double2 wc = INV ? make_double2(-wb.y, wb.x) : make_double2(wb.y, -wb.x);  // W_4h^(j+h)
   const double2 t1 = cmul(x1, wa), t3 = cmul(x3, wa);
   const double2 a0 = make_double2(x0.x + t1.x, x0.y + t1.y), a1 = make_double2(x0.x - t1.x, x0.y - t1.y);
@@ -108,19 +110,26 @@ __device__ __forceinline__ void fft_pass16(double2 *z, int pitch, int count, int
         x[a][b] = z[at[a][b]];
       }
     }
-    double2 wa = tw[j * st_a * tws];
-    double2 wb[4];
+    double2 wa = tw[j * st_a * tws], wa2 = tw[2 * j * st_a * tws];  // (2 j st_a < N / 2: inside the table)
+    double2 wb[4], wb2[4];
 #pragma unroll
-    for (int a = 0; a < 4; ++a) wb[a] = tw[(j + a * h) * st_b * tws];
+    for (int a = 0; a < 4; ++a) {
+      wb[a] = tw[(j + a * h) * st_b * tws];
+      wb2[a] = tw[2 * (j + a * h) * st_b * tws];
+    }
     if (INV) {
       wa.y = -wa.y;
+      wa2.y = -wa2.y;
 #pragma unroll
-      for (int a = 0; a < 4; ++a) wb[a].y = -wb[a].y;
+      for (int a = 0; a < 4; ++a) {
+        wb[a].y = -wb[a].y;
+        wb2[a].y = -wb2[a].y;
+      }
     }
 #pragma unroll
-    for (int b = 0; b < 4; ++b) radix4<INV>(x[0][b], x[1][b], x[2][b], x[3][b], wa);
+    for (int b = 0; b < 4; ++b) radix4<INV>(x[0][b], x[1][b], x[2][b], x[3][b], wa, wa2);
 #pragma unroll
-    for (int a = 0; a < 4; ++a) radix4<INV>(x[a][0], x[a][1], x[a][2], x[a][3], wb[a]);
+    for (int a = 0; a < 4; ++a) radix4<INV>(x[a][0], x[a][1], x[a][2], x[a][3], wb[a], wb2[a]);
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
 #pragma unroll
@@ -137,7 +146,7 @@ __device__ __forceinline__ void fft_pass16(double2 *z, int pitch, int count, int
 // disjoint elements) - written as one loop body, the compiler has to assume that a butterfly's
 // writes alias the next one's reads and serialises read -> compute -> write with the LDS / L2
 // latency exposed every time (the first version: 12 us per 4096-point transform instead of ~3).
-// Only W_4h^j is fetched per butterfly: W_2h^j is its square and W_4h^(j+h) = -i W_4h^j.
+// W_4h^j and W_2h^j are fetched per butterfly (see radix4 on why the second is not the first one's square); W_4h^(j+h) = -i W_4h^j.
 // `tw` is the table of a length N * tws (entry k * tws = exp(-2 pi i k / N)): sub-transforms of a
 // longer transform read the long table with a stride.
 // (Compile-time lengths - every shift, mask and twiddle stride an immediate, the pass loop unrolled - were
@@ -180,7 +189,7 @@ __device__ __forceinline__ void fft_lds(double2 *z, int pitch, int count, int lo
     const int total = (N >> 2) * count;
     for (int b0 = threadIdx.x; b0 < total; b0 += kU * static_cast<int>(blockDim.x)) {
       int i0[kU], i1[kU], i2[kU], i3[kU];
-      double2 x0[kU], x1[kU], x2[kU], x3[kU], w2[kU];
+      double2 x0[kU], x1[kU], x2[kU], x3[kU], w2[kU], w1[kU];
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int b = b0 + u * static_cast<int>(blockDim.x);
@@ -195,6 +204,7 @@ __device__ __forceinline__ void fft_lds(double2 *z, int pitch, int count, int lo
         i3[u] = base + lpad(e0 + 3 * h);
         if (live) {
           w2[u] = tw[j * st2 * tws];
+          w1[u] = tw[2 * j * st2 * tws];
           x0[u] = z[i0[u]];
           x1[u] = z[i1[u]];
           x2[u] = z[i2[u]];
@@ -204,9 +214,11 @@ __device__ __forceinline__ void fft_lds(double2 *z, int pitch, int count, int lo
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         if (i0[u] < 0) continue;
-        double2 wb = w2[u];
-        if (INV) wb.y = -wb.y;
-        const double2 wa = cmul(wb, wb);                                                  // W_2h^j
+        double2 wb = w2[u], wa = w1[u];  // W_4h^j, W_2h^j
+        if (INV) {
+          wb.y = -wb.y;
+          wa.y = -wa.y;
+        }
         const double2 wc = INV ? make_double2(-wb.y, wb.x) : make_double2(wb.y, -wb.x);  // W_4h^(j+h)
         const double2 t1 = cmul(x1[u], wa), t3 = cmul(x3[u], wa);
         const double2 a0 = make_double2(x0[u].x + t1.x, x0[u].y + t1.y), a1 = make_double2(x0[u].x - t1.x, x0[u].y - t1.y);

@@ -4,6 +4,9 @@ method (pysteps/utils/fft.py:20-37) - and through the reference's own callers.
 numpy's transforms are pocketfft in float64 [third party, numpy 2.2, installed]; the HIP
 kernels compute the same mathematical transform in float64 with a different factorisation, so
 parity is to round-off: rel-L2 <= 1e-12 (observed ~1e-16 x log2 size).
+
+A whole-array norm does not see an error confined to a few bins: tests/test_fft_pointwise_gpu.py holds every bin to
+numpy.fft in long double, per code path of fft.hip.
 """
 
 import numpy as np
