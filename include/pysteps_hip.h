@@ -528,6 +528,15 @@ int psh_lk_corners_finish(float *points_host, int *count_host);
 int psh_lk_pyramids_dev(const unsigned char *prev_u8_dev, const unsigned char *next_u8_dev, int m,
                         int n, int win_w, int win_h, int max_level, void **handle_out);
 int psh_lk_pyramids_free(void *handle);
+/* Read-out of a pyramid set (for tests; the trackers take the handle).  shape: geometry of `level` (0 .. top), the
+ * index of the coarsest level and whether the set holds a gradient image; any output pointer may be NULL.  read:
+ * one plane of a level to host memory - 0 the previous frame I, 1 the next frame J (rows * cols bytes; level 0 is
+ * the caller's uint8 frames), 2 the Scharr gradients of I (rows * cols interleaved int16 (Ix, Iy) pairs).  The copy
+ * is ordered behind the build on the stream the set was built on and is complete on return.  PSH_EINVAL, with
+ * nothing read, for a NULL handle, a level above top, nbytes other than the plane's size, and plane 2 of a set
+ * without a gradient image. */
+int psh_lk_pyramids_shape(void *handle, int level, int *rows, int *cols, int *top, int *has_deriv);
+int psh_lk_pyramids_read(void *handle, int level, int plane, void *host_out, size_t nbytes);
 
 /* Row bands of the image passes for frames tiled over several GPUs (BASELINE config 5).  Every rank
  * holds the whole frame and processes rows [e0, e1) - its own rows [r0, r1) plus a halo - as a

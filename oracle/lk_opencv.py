@@ -390,6 +390,146 @@ def calc_optical_flow_pyr_lk(prev_u8, next_u8, points, win=(50, 50), max_level=3
     return nxt, status
 
 
+def first_step(prev_u8, next_u8, points, win, min_eig_threshold=1e-4):
+    """ONE Lucas-Kanade iteration on level 0, with everything a test needs to hold an implementation to it.
+
+    The same arithmetic as ``calc_optical_flow_pyr_lk(..., max_level=0, max_count=1, epsilon=0)``.  Returns a
+    dict of arrays over the p points:
+
+    ``next`` (p,2) float32, ``status`` (p,) bool    the float32 result, operation by operation
+    ``sums`` (p,5) int64                            S11, S12, S22, T1, T2: exact window sums of gx gx, gx gy, gy gy,
+                                                    diff gx, diff gy (zero where the window was rejected)
+    ``stepped`` (p,) bool                           the iteration ran (window accepted, matrix not rejected)
+    ``d64`` (p,2) float64                           the step evaluated in float64 from the exact sums
+    ``bound`` (p,2) float64                         error bound of each component of ``next`` (inf: no step)
+    ``margin`` (p,) float64                         distance of the nearest status decision from its threshold,
+                                                    in units of that decision's float32 noise (> 1: clear)
+    ``patches``                                     per point (Ipatch, gx, gy, diff) int64 or None
+
+    The bound.  With a = S 2^-20 (a11, a12, a22 from S11, S12, S22; b1, b2 from T1, T2) the step is
+
+        D = a11 a22 - a12^2,   N1 = a12 b2 - a22 b1,   N2 = a12 b1 - a11 b2,   d = (N1, N2) / D,
+        next = ((p - half) + d) + half.
+
+    u = 2^-24 is the unit roundoff of float32; every line below is to first order in u.
+    * int -> float32 rounds once (|S| can exceed 2^24), the scaling by 2^-20 is exact: each a, b carries a relative
+      error u, each product of two of them 2u.
+    * A difference of two products x y - z w, evaluated either as fl(fl(x y) - fl(z w)) or with one product fused
+      into the subtraction (a compiler's contraction), errs by at most 2u (|x y| + |z w|): u per rounded product
+      and u on the result, |x y - z w| <= |x y| + |z w|.  With the inputs' 2u per product:
+          E(xy, zw) = 4u (|x y| + |z w|)     for D, N1 and N2.
+    * r = fl(1 / D) and d = fl(N r) add a relative u each; the errors of N and D pass through the quotient:
+          e_d = E_N / |D| + |N| E_D / D^2 + 2u |N / D|.
+    * q' = fl(q + d) and fl(q' + half) round once each.  Two evaluations whose d differ inside e_d may round to
+      neighbouring floats, so each addition is allowed one whole ulp at its magnitude:
+          bound = e_d + ulp32(|q + d|) + ulp32(|q + d + half|).
+    Two float32 evaluations that both respect the bound differ by at most 2 * bound; the float64 value differs
+    from each by at most bound.
+
+    Margins (float64, from the exact sums).  min_eig = ((a11 + a22) - sqrt((a11 - a22)^2 + 4 a12^2)) / (2 w h)
+    against the threshold: noise 8u (a11 + a22) / (2 w h) (sum, difference, square root and the subtraction that
+    cancels them).  D against FLT_EPSILON: noise E_D.  The window tests floor(p - half): p - half is ONE correctly
+    rounded float32 subtraction of the inputs on every side, so it has no noise unless the exact difference is
+    not representable; then its distance from the nearest integer is measured in ulps of the difference.  The
+    final window test rint(next - half) against -w and cols (rows): noise bound + 2 ulp.
+    """
+    f32 = np.float32
+    u = 2.0 ** -24
+    w, h = int(win[0]), int(win[1])
+    pts = np.asarray(points, dtype=np.float32).reshape(-1, 2)
+    npts = pts.shape[0]
+    rows, cols = prev_u8.shape
+    half = (f32((w - 1) * 0.5), f32((h - 1) * 0.5))
+    flt_scale = f32(1.0 / (1 << 20))
+    flt_eps = f32(np.finfo(np.float32).eps)
+    border = max(w, h) + 2
+    Ipad = _pad_reflect101(prev_u8.astype(np.int64), border)
+    Jpad = _pad_reflect101(next_u8.astype(np.int64), border)
+    dx, dy = scharr_deriv(prev_u8)
+    dxp = np.zeros((rows + 2 * border, cols + 2 * border), dtype=np.int64)
+    dyp = np.zeros_like(dxp)
+    dxp[border:-border, border:-border] = dx
+    dyp[border:-border, border:-border] = dy
+    out = {
+        "next": pts.copy(), "status": np.ones(npts, bool), "sums": np.zeros((npts, 5), np.int64),
+        "stepped": np.zeros(npts, bool), "d64": np.zeros((npts, 2)), "bound": np.full((npts, 2), np.inf),
+        "margin": np.full(npts, np.inf), "patches": [None] * npts,
+    }
+    lim = ((-w, cols), (-h, rows))
+
+    def floor_margin(p, hf):
+        exact = float(p) - float(hf)
+        got = float(f32(p - hf))
+        if got == exact:
+            return np.inf
+        return abs(exact - np.rint(exact)) / float(np.spacing(f32(abs(got))))
+
+    for i in range(npts):
+        ppx, ppy = f32(pts[i, 0] - half[0]), f32(pts[i, 1] - half[1])
+        ipx, ipy = int(np.floor(ppx)), int(np.floor(ppy))
+        margin = min(floor_margin(pts[i, 0], half[0]), floor_margin(pts[i, 1], half[1]))
+        out["margin"][i] = margin
+        if ipx < -w or ipx >= cols or ipy < -h or ipy >= rows:
+            out["status"][i] = False
+            continue
+        iw = _weights(ppx - f32(ipx), ppy - f32(ipy))
+        Ipatch = _bilinear_int(_window(Ipad, border, ipx, ipy, w, h), iw, 14 - 5)
+        gx = _bilinear_int(_window(dxp, border, ipx, ipy, w, h), iw, 14)
+        gy = _bilinear_int(_window(dyp, border, ipx, ipy, w, h), iw, 14)
+        diff = _bilinear_int(_window(Jpad, border, ipx, ipy, w, h), iw, 14 - 5) - Ipatch
+        S = [int((gx * gx).sum()), int((gx * gy).sum()), int((gy * gy).sum()), int((diff * gx).sum()),
+             int((diff * gy).sum())]
+        out["patches"][i] = (Ipatch, gx, gy, diff)
+        A11, A12, A22 = (f32(v) * flt_scale for v in S[:3])
+        D = f32(A11 * A22) - f32(A12 * A12)
+        disc = f32(f32(f32(A11 - A22) * f32(A11 - A22)) + f32(f32(4) * A12) * A12)
+        min_eig = f32(f32(A22 + A11) - np.sqrt(disc, dtype=np.float32)) / f32(2 * w * h)
+        # the same decisions in float64 from the exact sums, with their noise
+        a11, a12, a22, b1, b2 = (v / float(1 << 20) for v in S)
+        D64 = a11 * a22 - a12 * a12
+        E_D = 4 * u * (abs(a11 * a22) + a12 * a12)
+        eig64 = ((a11 + a22) - np.sqrt((a11 - a22) ** 2 + 4 * a12 * a12)) / (2 * w * h)
+        eig_noise = 8 * u * (a11 + a22) / (2 * w * h)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m_eig = abs(eig64 - min_eig_threshold) / eig_noise if eig_noise > 0 else np.inf
+            m_D = abs(D64 - float(flt_eps)) / E_D if E_D > 0 else np.inf
+        # (a matrix that fails the eigenvalue test clearly is rejected whatever D says)
+        rejected64 = eig64 < min_eig_threshold
+        margin = min(margin, m_eig if rejected64 else min(m_eig, m_D))
+        out["margin"][i] = margin
+        if min_eig < min_eig_threshold or D < flt_eps:
+            out["status"][i] = False
+            continue
+        out["sums"][i] = S
+        out["stepped"][i] = True
+        Dinv = f32(1) / D
+        B1, B2 = f32(S[3]) * flt_scale, f32(S[4]) * flt_scale
+        ddx = f32(f32(f32(A12 * B2) - f32(A22 * B1)) * Dinv)
+        ddy = f32(f32(f32(A12 * B1) - f32(A11 * B2)) * Dinv)
+        npx, npy = f32(ppx + ddx), f32(ppy + ddy)
+        out["next"][i] = (f32(npx + half[0]), f32(npy + half[1]))
+        N = (a12 * b2 - a22 * b1, a12 * b1 - a11 * b2)
+        E_N = (4 * u * (abs(a12 * b2) + abs(a22 * b1)), 4 * u * (abs(a12 * b1) + abs(a11 * b2)))
+        for c in range(2):
+            d = N[c] / D64
+            q = float(pts[i, c]) - float(half[c])
+            e_d = E_N[c] / abs(D64) + abs(N[c]) * E_D / (D64 * D64) + 2 * u * abs(d)
+            ulps = float(np.spacing(f32(abs(q + d)))) + float(np.spacing(f32(abs(q + d + float(half[c])))))
+            out["d64"][i, c] = d
+            out["bound"][i, c] = e_d + ulps
+            # the final window test: rint(next - half) in [lo, hi)
+            fin = q + d
+            noise = out["bound"][i, c] + 2 * float(np.spacing(f32(abs(fin))))
+            lo, hi = lim[c]
+            margin = min(margin, abs(fin - (lo - 0.5)) / noise, abs(fin - (hi - 0.5)) / noise)
+        out["margin"][i] = margin
+        fx, fy = f32(out["next"][i, 0] - half[0]), f32(out["next"][i, 1] - half[1])
+        rx, ry = int(_cv_round(fx)), int(_cv_round(fy))
+        if rx < -w or rx >= cols or ry < -h or ry >= rows:
+            out["status"][i] = False
+    return out
+
+
 def track_features(prev_img, next_img, prev_valid, next_valid, points, winsize=(50, 50), nr_levels=3,
                    max_count=10, epsilon=0.0, min_eig_thr=1e-4):
     """tracking/lucaskanade.py:130-189: per-frame min-max scaling to uint8, then pyramidal LK."""

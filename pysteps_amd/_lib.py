@@ -181,6 +181,8 @@ SIGNATURES = {
     "psh_lk_corners_finish": (c_int, [c_void_p, POINTER(c_int)]),
     "psh_lk_pyramids_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "psh_lk_pyramids_free": (c_int, [c_void_p]),
+    "psh_lk_pyramids_shape": (c_int, [c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "psh_lk_pyramids_read": (c_int, [c_void_p, c_int, c_int, c_void_p, c_size_t]),  # handle, level, plane, out, nbytes
     "psh_lk_pyramids_band": (c_int, [c_void_p, c_int, c_int, POINTER(c_int)]),  # handle, frame_rows, band_first_row, top
     "psh_lk_band_stats_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "psh_lk_band_open_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

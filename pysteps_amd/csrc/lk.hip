@@ -2573,6 +2573,7 @@ namespace {
 struct PyramidSet {
   psh::Pyramid pyr;
   void *block = nullptr;
+  hipStream_t stream = nullptr;  // the stream the levels were built on (psh_lk_pyramids_read copies behind them)
   int win_w = 0, win_h = 0, max_level = 0;
 };
 }  // namespace
@@ -2697,6 +2698,7 @@ static int lk_pyramids_on(hipStream_t stream, const unsigned char *prev_u8_dev, 
   ps->win_w = win_w;
   ps->win_h = win_h;
   ps->max_level = max_level;
+  ps->stream = stream;
   for (int l = 0; l <= top; ++l) {
     unsigned char *Il = l ? reinterpret_cast<unsigned char *>(base + off_i[l]) : const_cast<unsigned char *>(prev_u8_dev);
     unsigned char *Jl = l ? reinterpret_cast<unsigned char *>(base + off_j[l]) : const_cast<unsigned char *>(next_u8_dev);
@@ -2780,6 +2782,43 @@ int psh_lk_pyramids_free(void *handle) {
   if (ps->block && ctx().ready) rc = psh_free(ps->block);  // stream-ordered reuse
   delete ps;
   return rc;
+}
+
+// Read-out of a pyramid set for tests: geometry of a level, then one of its planes.  A band set
+// (psh_lk_pyramids_band) reports and hands out the rows it stores.
+int psh_lk_pyramids_shape(void *handle, int level, int *rows, int *cols, int *top, int *has_deriv) {
+  if (!handle) return fail(PSH_EINVAL, "lk_pyramids_shape: NULL handle");
+  const PyramidSet *ps = static_cast<const PyramidSet *>(handle);
+  if (level < 0 || level > ps->pyr.top)
+    return fail(PSH_EINVAL, "lk_pyramids_shape: level %d outside 0..%d", level, ps->pyr.top);
+  const psh::PyrLevel &L = ps->pyr.lv[level];
+  if (rows) *rows = std::min(L.rows, L.rows_stored);
+  if (cols) *cols = L.cols;
+  if (top) *top = ps->pyr.top;
+  if (has_deriv) *has_deriv = L.dI != nullptr ? 1 : 0;
+  return PSH_OK;
+}
+
+// plane 0: I, 1: J (rows * cols bytes), 2: dI (rows * cols int16 pairs).  The copy is queued on the stream the set
+// was built on, behind the kernels that fill the level, and has arrived when the call returns.
+int psh_lk_pyramids_read(void *handle, int level, int plane, void *host_out, size_t nbytes) {
+  if (!handle || !host_out) return fail(PSH_EINVAL, "lk_pyramids_read: NULL pointer");
+  PSH_REQUIRE_INIT();
+  const PyramidSet *ps = static_cast<const PyramidSet *>(handle);
+  if (level < 0 || level > ps->pyr.top)
+    return fail(PSH_EINVAL, "lk_pyramids_read: level %d outside 0..%d", level, ps->pyr.top);
+  if (plane < 0 || plane > 2) return fail(PSH_EINVAL, "lk_pyramids_read: plane %d outside 0..2", plane);
+  const psh::PyrLevel &L = ps->pyr.lv[level];
+  const void *src = plane == 0 ? static_cast<const void *>(L.I) : plane == 1 ? static_cast<const void *>(L.J) : L.dI;
+  if (!src) return fail(PSH_EINVAL, "lk_pyramids_read: the set has no gradient image (window of %d columns)", ps->win_w);
+  const size_t want = static_cast<size_t>(std::min(L.rows, L.rows_stored)) * L.cols * (plane == 2 ? sizeof(short2) : 1);
+  if (nbytes != want) return fail(PSH_EINVAL, "lk_pyramids_read: %zu bytes given, the plane holds %zu", nbytes, want);
+  psh::Context &c = ctx();
+  std::lock_guard<std::recursive_mutex> lock(c.mu);
+  PSH_HIP(hipSetDevice(c.device));
+  PSH_HIP(hipMemcpyAsync(host_out, src, want, hipMemcpyDeviceToHost, ps->stream));
+  PSH_HIP(hipStreamSynchronize(ps->stream));
+  return PSH_OK;
 }
 
 // picks the instantiation with the fewest window samples per thread

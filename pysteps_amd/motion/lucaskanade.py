@@ -146,6 +146,32 @@ class PyramidPair:
         )
         return p1, st.astype(bool)
 
+    def _shape(self, level):
+        rows, cols, top, deriv = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(
+            _lib.lib().psh_lk_pyramids_shape(self._h, int(level), ctypes.byref(rows), ctypes.byref(cols),
+                                             ctypes.byref(top), ctypes.byref(deriv)),
+            "psh_lk_pyramids_shape",
+        )
+        return rows.value, cols.value, top.value, bool(deriv.value)
+
+    @property
+    def top(self):
+        """Index of the coarsest level."""
+        return self._shape(0)[2]
+
+    def level(self, l):
+        """Level ``l`` on the host: (I, J, dI) - uint8 (rows, cols) each and int16 (rows, cols, 2) (Ix, Iy), or
+        None for dI when the window is narrow enough for the trackers to compute their gradients themselves."""
+        rows, cols, _, deriv = self._shape(l)
+        planes = [np.empty((rows, cols), np.uint8), np.empty((rows, cols), np.uint8)]
+        if deriv:
+            planes.append(np.empty((rows, cols, 2), np.int16))
+        for plane, out in enumerate(planes):
+            _lib.check(_lib.lib().psh_lk_pyramids_read(self._h, int(l), plane, out.ctypes.data, out.nbytes),
+                       "psh_lk_pyramids_read")
+        return planes[0], planes[1], planes[2] if deriv else None
+
     def close(self):
         if self._h:
             _lib.load().psh_lk_pyramids_free(self._h)
