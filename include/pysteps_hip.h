@@ -417,6 +417,29 @@ int psh_detcat_counts_dev(const void *fct_dev, int fct_f64, const void *obs_dev,
 int psh_detcont_sums_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int obs_f64, int obs_shared, int K, size_t npix,
                          int conditioning, double thr_fct, double thr_obs, unsigned long long *counts_dev, double *sums_dev);
 
+/* ---- probabilistic verification scores (csrc/probscores.hip) ------------------------------------------------------- *
+ * pysteps/verification/probscores.py CRPS_accum, reldiag_accum and ROC_curve_accum, float32 or float64 fields each on
+ * its own.  Both calls are queued on the library stream and return the same bits in every run and wherever a plane lies
+ * in a stack; the host tables are consumed before the call returns.
+ *
+ * psh_crps_sums_dev: n_planes observation planes of npix pixels, plane t against the K members (K, npix) at fct_dev
+ * (fct_shared) or against stack t of (n_planes, K, npix).  weights_host holds K + 1 pairs {(i/K)^2, ((K-i)/K)^2}.  A
+ * pixel takes part when its K members and its observation are finite; counts_dev (n_planes) receives their number and
+ * sums_dev (n_planes, 2) the sum of their CRPS (Hersbach's decomposition with the reference's strict inequalities: an
+ * observation equal to a member adds nothing from the bins it touches) as a double-double pair (hi, lo).  K <= 64.
+ *
+ * psh_probbins_dev: one probability plane and its observation; the pixels where both are finite take part.  With
+ * n_edges >= 2 non-decreasing bin edges (at most 65), bin b holds edges[b] < p <= edges[b + 1] (numpy.digitize with
+ * right=True): bins_dev (n_edges - 1, 2) receives its number of pixels and how many of them have obs >= x_min,
+ * sums_dev (n_edges - 1, 2) the sum of their probabilities as (hi, lo).  With n_prob_thrs thresholds (at most 64),
+ * roc_dev (n_prob_thrs, 4) receives hits (p >= thr, obs >= x_min), misses, false alarms and correct negatives.  Either
+ * table may be absent (count 0, pointers NULL).  All comparisons are float64 comparisons of the widened values. */
+int psh_crps_sums_dev(const void *fct_dev, int fct_f64, int fct_shared, const void *obs_dev, int obs_f64, int n_planes, int K,
+                      size_t npix, const double *weights_host, unsigned long long *counts_dev, double *sums_dev);
+int psh_probbins_dev(const void *prob_dev, int prob_f64, const void *obs_dev, int obs_f64, size_t npix, double x_min,
+                     const double *edges_host, int n_edges, const double *prob_thrs_host, int n_prob_thrs,
+                     unsigned long long *bins_dev, double *sums_dev, unsigned long long *roc_dev);
+
 /* ---- radially averaged power spectra (csrc/rapsd.hip) --------------------------------------------------------- *
  * pysteps/utils/spectral.py:100-180 (rapsd) for a stack of K planes: the mean power over the coefficients of every
  * integer radius r = round(sqrt(kx^2 + ky^2)) < nb, with l = max(m, n) and nb = l / 2 (+ 1 for odd l).  out_dev

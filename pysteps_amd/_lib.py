@@ -113,6 +113,9 @@ SIGNATURES = {
     "psh_detcat_counts_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
     "psh_detcont_sums_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_size_t, c_int, c_double, c_double, c_void_p,
                                      c_void_p]),
+    "psh_crps_sums_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "psh_probbins_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_double, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                 c_void_p, c_void_p]),
     "psh_rapsd_half_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "psh_rapsd_full_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "psh_rapsd_counts_dev": (c_int, [c_int, c_int, c_int, c_void_p]),

@@ -301,6 +301,42 @@ def unpatch_detscores():
         hip_mod._reference_fct = hip_mod._reference_fct_accum = None
 
 
+def patch_probscores():
+    """Replace ``CRPS``, ``reldiag`` and ``ROC_curve`` and their ``_accum`` functions in
+    ``pysteps.verification.probscores`` by the device versions (:mod:`pysteps_amd.verification.probscores`).
+    ``pysteps.verification.interface.get_method`` imports the three one-shot functions from that module when it is
+    called (interface.py:239) and there is no table to add a name to, so the attributes are what has to change.  The
+    ``_init`` and ``_compute`` functions stay the reference's: objects of either side are interchangeable.  Inputs the
+    device path declines run the reference's ``_accum`` functions, which stay reachable."""
+    import pysteps.verification.probscores as ref_mod  # noqa: PLC0415
+
+    from .verification import probscores as hip_mod  # noqa: PLC0415
+
+    if ref_mod.CRPS_accum is hip_mod.CRPS_accum:
+        return []
+    added = []
+    for name in hip_mod.SWAPPED:
+        setattr(ref_mod, "_reference_" + name, getattr(ref_mod, name))
+        hip_mod._held[name] = getattr(ref_mod, name)
+        setattr(ref_mod, name, getattr(hip_mod, name))
+        added.append("verification:" + name)
+    return added
+
+
+def unpatch_probscores():
+    """Undo :func:`patch_probscores`."""
+    import pysteps.verification.probscores as ref_mod  # noqa: PLC0415
+
+    from .verification import probscores as hip_mod  # noqa: PLC0415
+
+    for name in hip_mod.SWAPPED:
+        ref = getattr(ref_mod, "_reference_" + name, None)
+        if ref is not None:
+            setattr(ref_mod, name, ref)
+            delattr(ref_mod, "_reference_" + name)
+    hip_mod._held.clear()
+
+
 def patch_noise_stddev_adj():
     """Replace ``pysteps.noise.utils.compute_noise_stddev_adjs`` by the device version
     (:mod:`pysteps_amd.noise.utils`).  ``nowcasts.steps`` with ``noise_stddev_adj="auto"`` looks the function up as
@@ -397,7 +433,7 @@ def register_postprocessing(override=False):
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
-             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False, rapsd=False):
+             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False, rapsd=False, probscores=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -417,7 +453,9 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     :func:`unpatch_noise_stddev_adj` undoes it).  ``detscores=True`` makes ``pysteps.verification`` count contingency
     tables and sum the continuous error moments on the device (:func:`patch_detscores`; :func:`unpatch_detscores`
     undoes it).  ``rapsd=True`` makes ``pysteps.utils.spectral.rapsd`` bin its spectra on the device
-    (:func:`patch_rapsd`; :func:`unpatch_rapsd` undoes it)."""
+    (:func:`patch_rapsd`; :func:`unpatch_rapsd` undoes it).  ``probscores=True`` makes
+    ``pysteps.verification.probscores`` accumulate the CRPS, reliability diagrams and ROC curves on the device
+    (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -451,6 +489,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += patch_detscores()
     if rapsd:
         added += patch_rapsd()
+    if probscores:
+        added += patch_probscores()
     if patch_main_loop:
         import importlib  # noqa: PLC0415
 
