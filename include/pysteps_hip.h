@@ -484,6 +484,30 @@ int psh_darts_rows_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int
 int psh_darts_synth_dev(const int *ky_host, const int *kx_host, const void *values_host, int nb, int m, int n, int f32,
                         void *out_dev);
 
+/* ---- RainFARM stochastic downscaling (csrc/rainfarm.hip) ------------------------------------------------------ *
+ * pysteps/downscaling/rainfarm.py ``downscale`` without spectral fusion for K realisations; (m, n) is the
+ * low-resolution shape, ds the factor, (M, N) = (m ds, n ds); float64; every call is queued on the library stream.
+ *  psh_rainfarm_spectrum_dev  u (K, M, N) uniforms, alphas (K) -> half (K, M, N/2+1) complex128: the Hermitian part
+ *      of exp(2 pi i u) sqrt(f^-alpha) with f = hypot(fftfreq_i, fftfreq_j), fftfreq = signed bin * vi (vj); the DC
+ *      bin is 0.  psh_fft_irfft2_dev of a plane is Re(ifft2) of the reference's full spectrum.
+ *  psh_rainfarm_std_dev       stats (K, 2) = {mean, population standard deviation} of K planes: the mean first, then
+ *      the mean squared deviation, double-double sums in a fixed order.
+ *  psh_rainfarm_exp_dev       e (K, M, N) = exp(noise / stats[.][1]) (e == noise allowed), agg (K, m, n) = its
+ *      ds x ds block means, along rows first.
+ *  psh_rainfarm_finish_dev    out (K, M, N) float32 (f32) or float64 = e S(precip) / S(agg), values below `threshold`
+ *      set to 0 if has_threshold; precip (precip_planes, m, n) with precip_planes 1 or K.  table NULL: S expands to
+ *      the fine grid.  Else table (ds, ds, na, na): the smoothing-kernel weight that reaches the coarse cell
+ *      (I + a + amin, J + b + amin) from a pixel at phase (py, px) of cell (I, J); S is the reference's balanced
+ *      spatial average. */
+int psh_rainfarm_spectrum_dev(const double *u_dev, const double *alphas_dev, int K, int M, int N, double vi, double vj,
+                              void *half_dev);
+int psh_rainfarm_std_dev(const double *noise_dev, int K, size_t plane, double *stats_dev);
+int psh_rainfarm_exp_dev(const double *noise_dev, const double *stats_dev, int K, int m, int n, int ds, double *e_dev,
+                         double *agg_dev);
+int psh_rainfarm_finish_dev(const double *e_dev, const double *precip_dev, int precip_planes, const double *agg_dev, int K,
+                            int m, int n, int ds, const double *table_dev, int na, int amin, int has_threshold,
+                            double threshold, int f32, void *out_dev);
+
 /* ---- dense Lucas-Kanade: image front end ----------------------------------- *
  * The NumPy + OpenCV stages of pysteps/motion/lucaskanade.py:205-242, per frame /
  * frame pair.  OpenCV is a third-party dependency of the reference (not in its

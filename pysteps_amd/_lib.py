@@ -126,6 +126,11 @@ SIGNATURES = {
     "psh_darts_gram_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p]),
     "psh_darts_rows_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     "psh_darts_synth_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "psh_rainfarm_spectrum_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p]),
+    "psh_rainfarm_std_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
+    "psh_rainfarm_exp_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "psh_rainfarm_finish_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                        c_int, c_int, c_double, c_int, c_void_p]),
     "psh_steps_mask_probmatch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psh_dilated_mask_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "psh_steps_incremental_mask_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -373,8 +373,10 @@ def patch_rapsd():
     ``pysteps.utils.interface.get_method("rapsd")`` builds its table from ``spectral.rapsd`` when it is called and
     ``noise.fftgenerators.initialize_param_2d_fft_filter`` calls ``utils.spectral.rapsd`` (fftgenerators.py:150), so both
     go through the device after the swap; inputs the device path declines run the reference's function with a
-    ``RuntimeWarning``.  ``downscaling.rainfarm`` binds the name when it is imported (``from ..utils.spectral import
-    rapsd``) and keeps the reference's function."""
+    ``RuntimeWarning``.  The reference's ``downscaling.rainfarm`` binds the name when it is imported (``from
+    ..utils.spectral import rapsd``), uses it for spectral fusion alone and keeps the reference's function; the device
+    RainFARM (``"rainfarm_hip"``, :func:`register_downscaling`) hands spectral fusion to the reference and needs no
+    ``rapsd``."""
     import pysteps.utils.spectral as ref_mod  # noqa: PLC0415
 
     from .utils import spectral as hip_mod  # noqa: PLC0415
@@ -413,6 +415,17 @@ def register_nowcasts():
     now_if._nowcast_methods["anvil_hip"] = forecast
     now_if._nowcast_methods["lagrangian_probability_hip"] = lagprob_forecast
     return ["nowcast:anvil_hip", "nowcast:lagrangian_probability_hip"]
+
+
+def register_downscaling():
+    """Add ``"rainfarm_hip"`` (:func:`pysteps_amd.downscaling.rainfarm.downscale`) to pysteps' downscaling table
+    (pysteps/downscaling/interface.py ``_downscale_methods``); the stock ``"rainfarm"`` stays the reference's."""
+    import pysteps.downscaling.interface as ds_if  # noqa: PLC0415
+
+    from .downscaling.rainfarm import downscale  # noqa: PLC0415
+
+    ds_if._downscale_methods["rainfarm_hip"] = downscale
+    return ["downscaling:rainfarm_hip"]
 
 
 def register_postprocessing(override=False):
@@ -455,7 +468,9 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     undoes it).  ``rapsd=True`` makes ``pysteps.utils.spectral.rapsd`` bin its spectra on the device
     (:func:`patch_rapsd`; :func:`unpatch_rapsd` undoes it).  ``probscores=True`` makes
     ``pysteps.verification.probscores`` accumulate the CRPS, reliability diagrams and ROC curves on the device
-    (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it)."""
+    (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it).
+
+    ``"rainfarm_hip"`` joins ``pysteps.downscaling``'s method table (:func:`register_downscaling`)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -472,6 +487,10 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += register_postprocessing(override=override)
     except ImportError:
         pass  # pysteps.postprocessing imports its diagnostics' optional dependencies lazily; a stripped-down install may lack it
+    try:
+        added += register_downscaling()
+    except ImportError:
+        pass  # an older or stripped-down install may lack pysteps.downscaling
     if fft:
         added += register_fft()
         added += register_spectral()
