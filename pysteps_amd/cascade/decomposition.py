@@ -18,6 +18,7 @@ import weakref
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray
 from ..utils import fft as hip_fft
 
@@ -66,20 +67,25 @@ def _device_nonfinite(field):
     return count.value > 0
 
 
-def _reference_decomposition():
-    try:
-        from pysteps.cascade.decomposition import decomposition_fft as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is decomposition_fft else ref
-
-
-def _reference_recompose():
-    try:
-        from pysteps.cascade.decomposition import recompose_fft as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is recompose_fft else ref
+def _self_conjugate_columns_symmetric(planes, n):
+    """The spectral form of the update reads level variances off the spectrum (Parseval), which needs every product
+    ``spectrum x weights`` to stay Hermitian: a real filter has to take the same value at (ky, kx) and (-ky, kx) on the
+    two columns of an rfft2 half spectrum that are their own mirror images (kx = 0 and, for even n, the Nyquist column).
+    Filters that are functions of |k| - every band-pass filter and noise filter pysteps builds - are; anything else
+    keeps the chain of spatial operators.  ``planes``: (..., m, n // 2 + 1) NumPy array; DeviceArrays are trusted."""
+    if isinstance(planes, DeviceArray):
+        return True
+    a = np.asarray(planes)
+    if a.ndim < 2 or a.shape[-1] != n // 2 + 1 or np.iscomplexobj(a):
+        return False
+    cols = [0] + ([a.shape[-1] - 1] if n % 2 == 0 else [])
+    for c in cols:
+        col = a[..., :, c]
+        mirrored = np.concatenate([col[..., :1], col[..., :0:-1]], axis=-1)
+        scale = float(np.max(np.abs(col))) if col.size else 0.0
+        if not np.allclose(col, mirrored, rtol=1e-9, atol=1e-12 * scale):
+            return False
+    return True
 
 
 def decomposition_fft(field, bp_filter, **kwargs):
@@ -102,7 +108,7 @@ def decomposition_fft(field, bp_filter, **kwargs):
         and output_domain == "spatial" and (resident or np.asarray(field).dtype != np.float32)
     )
     if not on_device:
-        ref = _reference_decomposition()
+        ref = lookup("cascade.decomposition", "decomposition_fft", decomposition_fft)
         if ref is None or resident:
             raise NotImplementedError(
                 "pysteps_amd decomposition_fft: only spatial -> spatial, unmasked, power-of-two fields "
@@ -186,7 +192,7 @@ def recompose_fft(decomp, **kwargs):
         return recompose_fft(on_device).to_host()
     if not isinstance(levels, DeviceArray):
         # everything else (small cascades, spectral / compact ones): the reference's own function
-        ref = _reference_recompose()
+        ref = lookup("cascade.decomposition", "recompose_fft", recompose_fft)
         if ref is None:
             raise NotImplementedError("pysteps_amd recompose_fft: this cascade is not taken by the HIP path and pysteps is not "
                                       "importable for the reference's recompose_fft")

@@ -120,6 +120,24 @@ class DeviceArray:
         return "DeviceArray(shape=%s, dtype=%s, ptr=0x%x)" % (self.shape, self.dtype, self.ptr)
 
 
+def _dtype_of(X):
+    return X.dtype if isinstance(X, DeviceArray) else np.asanyarray(X).dtype
+
+
+def _upload(X):
+    if isinstance(X, DeviceArray):
+        return X
+    return DeviceArray.from_host(np.ascontiguousarray(np.asarray(X)), sync=False)
+
+
+def _compared_as(x, dtype):
+    """The float64 number that decides ``X >= x`` / ``X < x`` for a stack of ``dtype`` as NumPy evaluates it."""
+    if dtype == np.float32 and np.result_type(np.float32, x) == np.float32:
+        with np.errstate(over="ignore"):
+            return float(np.float32(x))
+    return float(x)
+
+
 def synchronize():
     _lib.check(_lib.lib().psh_sync(), "psh_sync")
 

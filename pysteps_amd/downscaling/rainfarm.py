@@ -33,6 +33,7 @@ import warnings
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray, Event, synchronize
 from ..noise.randstate import DeviceRandomStates
 from ..utils import fft as hip_fft
@@ -206,14 +207,6 @@ def finish(precip, noise, ds_factor, kernel_type=None, threshold=None, out_dtype
     return out.view(0) if single else out
 
 
-def _reference_downscale():
-    try:
-        from pysteps.downscaling.rainfarm import downscale as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is downscale else ref
-
-
 def _unsupported(shape, dtype, ds, spectral_fusion):
     """Why the device path does not take this call (None if it does)."""
     if spectral_fusion:
@@ -230,7 +223,7 @@ def _unsupported(shape, dtype, ds, spectral_fusion):
 
 def _run_reference(why, fields, resident, ds_factor, randstate, kw):
     """The reference's ``downscale`` on every field in turn, drawing from ``randstate`` when one is given."""
-    ref = _reference_downscale()
+    ref = lookup("downscaling.rainfarm", "downscale", downscale)
     if ref is None:
         raise NotImplementedError("pysteps_amd rainfarm: %s, and pysteps is not importable for the reference's downscale" % why)
     if isinstance(randstate, DeviceRandomStates):

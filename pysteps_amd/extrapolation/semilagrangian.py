@@ -27,6 +27,7 @@ import weakref
 import numpy as np
 
 from .. import _lib, _pinned
+from .._reference import lookup
 from ..device import DeviceArray
 
 __all__ = ["extrapolate"]
@@ -42,16 +43,8 @@ _BOUNDARY_MODES = {"constant": 0, "nearest": 1, "reflect": 2, "mirror": 3, "wrap
                    "grid-constant": 5, "grid-wrap": 6}
 
 
-def _reference_extrapolate():
-    try:
-        from pysteps.extrapolation.semilagrangian import extrapolate as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is extrapolate else ref
-
-
 def _unsupported(what, args, kwargs):
-    ref = _reference_extrapolate()
+    ref = lookup("extrapolation.semilagrangian", "extrapolate", extrapolate)
     if ref is None:
         raise NotImplementedError(
             "pysteps_amd semilagrangian: %s is not implemented on the HIP path and the "

@@ -21,6 +21,7 @@ import numpy as np
 from scipy import spatial
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray
 
 __all__ = ["detection", "response_cube"]
@@ -184,11 +185,8 @@ def detection(input_image, max_num_features=None, method="log", threshold=0.5, m
     elif not isinstance(input_image, DeviceArray) and np.asarray(input_image).dtype not in (np.float32, np.float64):
         unsupported = "images of dtype %s" % np.asarray(input_image).dtype
     if unsupported is not None:
-        try:
-            from pysteps.feature.blob import detection as ref  # noqa: PLC0415
-        except Exception as exc:
-            raise NotImplementedError("pysteps_amd blob.detection: %s is not implemented on the HIP path" % unsupported) from exc
-        if ref is detection or isinstance(input_image, DeviceArray):
+        ref = lookup("feature.blob", "detection", detection)
+        if ref is None or isinstance(input_image, DeviceArray):
             raise NotImplementedError("pysteps_amd blob.detection: %s is not implemented on the HIP path" % unsupported)
         warnings.warn("pysteps_amd blob.detection: %s -> delegating to the reference CPU path" % unsupported)
         return ref(input_image, max_num_features, method, threshold, min_sigma, max_sigma, overlap, return_sigmas, **kwargs)

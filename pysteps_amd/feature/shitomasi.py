@@ -11,6 +11,7 @@ import warnings
 
 import numpy as np
 
+from .._reference import lookup
 from ..device import DeviceArray
 
 __all__ = ["detection"]
@@ -26,13 +27,12 @@ def detection(input_image, max_corners=1000, max_num_features=None, quality_leve
         raise ValueError("input_image must be a two-dimensional array")
     supported = not use_harris and isinstance(block_size, (int, np.integer)) and 1 <= block_size <= 7 and block_size % 2 == 1
     if not supported:
-        try:
-            from pysteps.feature.shitomasi import detection as ref  # noqa: PLC0415
-        except Exception as exc:
+        ref = lookup("feature.shitomasi", "detection", detection)
+        if ref is None:
             raise NotImplementedError(
                 "pysteps_amd shitomasi.detection: use_harris / block_size=%r is not implemented on the HIP path" % (block_size,)
-            ) from exc
-        if ref is detection or isinstance(input_image, DeviceArray):
+            )
+        if isinstance(input_image, DeviceArray):
             raise NotImplementedError("pysteps_amd shitomasi.detection: use_harris / block_size=%r" % (block_size,))
         warnings.warn("pysteps_amd shitomasi.detection: delegating to the reference CPU path")
         return ref(input_image, max_corners, max_num_features, quality_level, min_distance, block_size, buffer_mask,

@@ -28,6 +28,7 @@ import warnings
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray, Event, synchronize
 from ..utils import fft as hip_fft
 
@@ -96,14 +97,6 @@ def _unsupported(shape, o):
     if 2 * (2 * o["M_x"] + 1) * (2 * o["M_y"] + 1) > MAX_COLUMNS:
         return "M_x=%d, M_y=%d (the device path takes at most %d unknowns)" % (o["M_x"], o["M_y"], MAX_COLUMNS)
     return None
-
-
-def _reference_darts():
-    try:
-        from pysteps.motion.darts import DARTS as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is DARTS else ref
 
 
 def band_cube(frames, N_y, N_x, N_t, M_y=0, M_x=0):
@@ -222,7 +215,7 @@ def DARTS(input_images, **kwargs):
 
     why = _unsupported(tuple(input_images.shape), o)
     if why is not None:
-        ref = _reference_darts()
+        ref = lookup("motion.darts", "DARTS", DARTS)
         if ref is None:
             raise NotImplementedError("pysteps_amd DARTS: %s, and pysteps is not importable for the reference's DARTS"
                                       % why)

@@ -28,6 +28,7 @@ import warnings
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray
 from ..utils.cleansing import decluster, detect_outliers_device
 from ..utils.interpolate import idw_to_device, idwinterp2d
@@ -280,14 +281,6 @@ def _blob_points(prep, host_frame, fd_kwargs):
     return detection(image, **kwargs).astype(np.float32)
 
 
-def _reference_dense_lk():
-    try:
-        from pysteps.motion.lucaskanade import dense_lucaskanade as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is dense_lucaskanade else ref
-
-
 def _dense_with_reference_interpolator(input_images, lk_kwargs, fd_method, fd_kwargs, interp_method, interp_kwargs,
                                        nr_std_outlier, k_outlier, size_opening, decl_scale, verbose):
     """Another interpolation method: the sparse stage - features, tracking, outlier removal - runs on the HIP
@@ -303,13 +296,12 @@ def _dense_with_reference_interpolator(input_images, lk_kwargs, fd_method, fd_kw
         # SciPy's own weights, the grid evaluation on the device (utils/interpolate.py, csrc/rbf.hip)
         from ..utils.interpolate import rbfinterp2d as interpolation_method  # noqa: PLC0415
     else:
-        try:
-            from pysteps import utils as ref_utils  # noqa: PLC0415
-        except Exception as exc:
+        get_method = lookup("utils", "get_method", None)
+        if get_method is None:
             raise NotImplementedError(
                 "pysteps_amd dense_lucaskanade: interp_method=%r needs pysteps' interpolation functions" % (interp_method,)
-            ) from exc
-        interpolation_method = ref_utils.get_method(interp_method)  # ValueError for unknown names, as the reference
+            )
+        interpolation_method = get_method(interp_method)  # ValueError for unknown names, as the reference
     xy, uv = dense_lucaskanade(
         input_images, lk_kwargs, fd_method, fd_kwargs, "idwinterp2d", None, False, nr_std_outlier, k_outlier,
         size_opening, decl_scale, verbose,
@@ -400,7 +392,7 @@ def dense_lucaskanade(
             unsupported = "interp_kwargs power=%r (> 0 on the HIP path)" % (ipow,)
 
     if unsupported is not None:
-        ref = _reference_dense_lk()
+        ref = lookup("motion.lucaskanade", "dense_lucaskanade", dense_lucaskanade)
         if ref is None or isinstance(input_images, DeviceArray):
             raise NotImplementedError(
                 "pysteps_amd dense_lucaskanade: %s is not implemented on the HIP path" % unsupported

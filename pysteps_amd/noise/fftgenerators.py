@@ -16,17 +16,10 @@ The filter array is uploaded once and kept on the device while the filter dictio
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..cascade.decomposition import _device_weights
 from ..device import DeviceArray
 from ..utils import fft as hip_fft
-
-
-def _reference_generator():
-    try:
-        from pysteps.noise.fftgenerators import generate_noise_2d_fft_filter as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is generate_noise_2d_fft_filter else ref
 
 
 def generate_noise_2d_fft_filter(F, randstate=None, seed=None, fft_method=None, domain="spatial"):
@@ -56,7 +49,7 @@ def generate_noise_2d_fft_filter(F, randstate=None, seed=None, fft_method=None, 
 
     if domain != "spatial" or use_full_fft or not hip_fft.supported_shape(input_shape):
         # the reference's own generator (fftgenerators.py:398-437) with the HIP transforms where they apply
-        ref = _reference_generator()
+        ref = lookup("noise.fftgenerators", "generate_noise_2d_fft_filter", generate_noise_2d_fft_filter)
         if ref is None:
             raise NotImplementedError("pysteps_amd generate_noise_2d_fft_filter: spatial domain, half-spectrum filters and "
                                       "power-of-two grids run on the HIP path; pysteps is not importable for the rest")

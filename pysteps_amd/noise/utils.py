@@ -22,7 +22,8 @@ import warnings
 import numpy as np
 
 from .. import _lib
-from ..cascade.decomposition import _device_weights
+from .._reference import _is_fn, lookup
+from ..cascade.decomposition import _device_weights, _self_conjugate_columns_symmetric
 from ..device import DeviceArray
 from ..utils import fft as hip_fft
 from .randstate import DeviceRandomStates
@@ -38,28 +39,6 @@ BATCH_BYTES = 8 << 30
 # plane is less than what the fourfold accumulators cost, so every plane reads the mask itself
 PLANES_PER_BLOCK = 1
 
-_reference_fn = None  # the reference's function while register.patch_noise_stddev_adj() has replaced it
-
-
-def _is_fn(obj, module_suffix, name):
-    """``obj`` is the function ``name`` of a module ending in ``module_suffix`` (the reference's or ours)."""
-    return callable(obj) and getattr(obj, "__name__", "") == name and getattr(obj, "__module__", "").endswith(module_suffix)
-
-
-def _self_conjugate_columns_symmetric(planes, n):
-    from ..nowcasts.steps_resident import _self_conjugate_columns_symmetric as check  # noqa: PLC0415
-
-    return check(planes, n)
-
-
-def _reference():
-    if _reference_fn is not None:
-        return _reference_fn
-    try:
-        from pysteps.noise.utils import compute_noise_stddev_adjs as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is compute_noise_stddev_adjs else ref
 
 
 def _seed_chain(seed, num_iter):
@@ -120,7 +99,7 @@ def _decline_reason(R, R_thr_1, F, decomp_method, noise_filter, noise_generator,
 
 
 def _to_reference(reason, R, args, kwargs):
-    ref = _reference()
+    ref = lookup("noise.utils", "compute_noise_stddev_adjs", compute_noise_stddev_adjs)
     if ref is None:
         raise NotImplementedError("pysteps_amd compute_noise_stddev_adjs: %s, and pysteps is not importable for the "
                                   "reference's function" % reason)

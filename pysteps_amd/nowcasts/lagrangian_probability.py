@@ -23,6 +23,7 @@ import warnings
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray
 from . import extrapolation
 
@@ -91,14 +92,6 @@ def probability_stage(fields, threshold, scales):
     return out
 
 
-def _reference_forecast():
-    try:
-        from pysteps.nowcasts.lagrangian_probability import forecast as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is forecast else ref
-
-
 def _unsupported(precip, leads, slope, extrap_method, extrap_kwargs):
     if not isinstance(extrap_method, str) or extrap_method.lower() not in _EXTRAPOLATORS:
         return "extrap_method=%r" % (extrap_method,)
@@ -163,7 +156,7 @@ def forecast(precip, velocity, timesteps, threshold, extrap_method="semilagrangi
 
     why = _unsupported(precip, leads, slope, extrap_method, extrap_kwargs)
     if why is not None:
-        ref = _reference_forecast()
+        ref = lookup("nowcasts.lagrangian_probability", "forecast", forecast)
         if ref is None or resident_in:
             raise NotImplementedError("pysteps_amd lagrangian_probability: %s is not implemented on the device and "
                                       "pysteps is not importable for the reference's forecast" % why)

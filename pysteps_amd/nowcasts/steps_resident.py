@@ -49,7 +49,8 @@ import os
 import numpy as np
 
 from .. import _lib
-from ..cascade.decomposition import _device_weights
+from .._reference import _is_fn, require
+from ..cascade.decomposition import _device_weights, _self_conjugate_columns_symmetric
 from ..device import DeviceArray
 from ..noise.randstate import DeviceRandomStates
 from ..utils import fft as hip_fft
@@ -57,11 +58,6 @@ from ..utils import fft as hip_fft
 __all__ = ["ResidentSteps", "try_create", "recognises"]
 
 _MAX_LEVELS, _MAX_ORDER = 16, 8
-
-
-def _is_fn(obj, module_suffix, name):
-    """``obj`` is the function ``name`` of a module ending in ``module_suffix`` (the reference's or ours)."""
-    return callable(obj) and getattr(obj, "__name__", "") == name and getattr(obj, "__module__", "").endswith(module_suffix)
 
 
 def _c_doubles(values):
@@ -98,27 +94,6 @@ def _spectral_std_of_moduli(x, m, n):
     res = np.sum(x ** 2) - x[0, 0] ** 2
     res += np.sum(x[:, 1:] ** 2) if n % 2 == 1 else np.sum(x[:, 1:-1] ** 2)
     return np.sqrt(res / (m * n) ** 2)
-
-
-def _self_conjugate_columns_symmetric(planes, n):
-    """The spectral form of the update reads level variances off the spectrum (Parseval), which needs every product
-    ``spectrum x weights`` to stay Hermitian: a real filter has to take the same value at (ky, kx) and (-ky, kx) on the
-    two columns of an rfft2 half spectrum that are their own mirror images (kx = 0 and, for even n, the Nyquist column).
-    Filters that are functions of |k| - every band-pass filter and noise filter pysteps builds - are; anything else
-    keeps the chain of spatial operators.  ``planes``: (..., m, n // 2 + 1) NumPy array; DeviceArrays are trusted."""
-    if isinstance(planes, DeviceArray):
-        return True
-    a = np.asarray(planes)
-    if a.ndim < 2 or a.shape[-1] != n // 2 + 1 or np.iscomplexobj(a):
-        return False
-    cols = [0] + ([a.shape[-1] - 1] if n % 2 == 0 else [])
-    for c in cols:
-        col = a[..., :, c]
-        mirrored = np.concatenate([col[..., :1], col[..., :0:-1]], axis=-1)
-        scale = float(np.max(np.abs(col))) if col.size else 0.0
-        if not np.allclose(col, mirrored, rtol=1e-9, atol=1e-12 * scale):
-            return False
-    return True
 
 
 def try_create(func, state, params, shape, n_updates):
@@ -578,9 +553,7 @@ class ResidentSteps:
         thr = ctypes.c_double()
         rc = lib.psh_order_statistic_dev(self.det_field.ptr, plane, self.det_index, ctypes.byref(thr))
         if rc == _lib.PSH_EUNSUPPORTED:  # a value plateau the bucket pass declines: the reference's sort
-            from pysteps.nowcasts.utils import compute_percentile_mask  # noqa: PLC0415
-
-            mask = compute_percentile_mask(self.det_field.to_host(), self.war)
+            mask = require("nowcasts.utils", "compute_percentile_mask", None)(self.det_field.to_host(), self.war)
             self.keep = DeviceArray.from_host(np.ascontiguousarray(mask, dtype=np.uint8))
             return
         _lib.check(rc, "psh_order_statistic_dev")
@@ -589,9 +562,9 @@ class ResidentSteps:
     def _probmatch_on_host(self, field):
         """The device CDF matching declined (thousands of tied wet values, infinities in the target):
         this one call goes through the reference's function and comes back."""
-        from ..postprocessing.probmatching import _reference  # noqa: PLC0415
+        from ..postprocessing.probmatching import _stock  # noqa: PLC0415
 
-        got = _reference()(field.to_host(), np.asarray(self.target.to_host(), dtype=np.float64))
+        got = _stock()(field.to_host(), np.asarray(self.target.to_host(), dtype=np.float64))
         return DeviceArray.from_host(np.ascontiguousarray(got, dtype=np.float64))
 
     def finish(self):

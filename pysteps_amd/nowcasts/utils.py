@@ -23,6 +23,7 @@ import numpy as np
 
 from .. import _lib
 from .. import extrapolation as _hip_extrapolation
+from .._reference import lookup, require
 from ..device import DeviceArray
 from ..extrapolation.ensemble import EnsembleAdvector
 from ..extrapolation.semilagrangian import extrapolate as _hip_extrapolate
@@ -65,18 +66,6 @@ class _Timeline:
         for (_, e0), (name, e1) in zip(self.marks[:-1], self.marks[1:]):
             out[name] = out.get(name, 0.0) + ((e1 - e0) * 1e3 if self.wall else e0.elapsed_ms(e1))
         return out
-_reference_dilated_mask = None  # set by register.patch_dilated_mask(): the function this module replaced
-
-
-def _reference_compute_dilated_mask():
-    if _reference_dilated_mask is not None:
-        return _reference_dilated_mask
-    from pysteps.nowcasts import utils as ref_mod  # noqa: PLC0415
-
-    fn = getattr(ref_mod, "_reference_compute_dilated_mask", ref_mod.compute_dilated_mask)
-    if fn is compute_dilated_mask:
-        raise NotImplementedError("the reference's compute_dilated_mask is not reachable")
-    return fn
 
 
 def compute_dilated_mask(input_mask, kr, r):
@@ -106,7 +95,7 @@ def compute_dilated_mask(input_mask, kr, r):
         d_mask = input_mask
     else:
         if not eligible or shape[0] * shape[1] < MIN_HOST_MASK:
-            return _reference_compute_dilated_mask()(input_mask, kr, r)
+            return require("nowcasts.utils", "compute_dilated_mask", compute_dilated_mask)(input_mask, kr, r)
         # utils.py:87: the mask is cast to uint8 first (a value of 0.5 becomes 0, 256 wraps to 0)
         d_mask = DeviceArray.from_host(np.ndarray.astype(np.asarray(input_mask), "uint8"), sync=False)
     out = DeviceArray(shape, np.float64)
@@ -329,14 +318,8 @@ def nowcast_main_loop(precip, velocity, state, timesteps, extrap_method, func, e
         from .anvil import try_create as anvil_resident  # noqa: PLC0415
 
         anvil = anvil_resident(func, state)
-    try:
-        if anvil is not None:
-            raise ImportError
-        from pysteps import extrapolation as ref_extrapolation  # noqa: PLC0415
-
-        extrapolator = ref_extrapolation.get_method(extrap_method)
-    except ImportError:
-        extrapolator = _hip_extrapolation.get_method(extrap_method)
+    get_extrapolator = None if anvil is not None else lookup("extrapolation", "get_method", None)
+    extrapolator = (get_extrapolator or _hip_extrapolation.get_method)(extrap_method)
 
     n_members = num_ensemble_members if ensemble else 1
     engine = None

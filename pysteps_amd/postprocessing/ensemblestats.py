@@ -30,7 +30,8 @@ import warnings
 import numpy as np
 
 from .. import _lib
-from ..device import DeviceArray
+from .._reference import decline, lookup
+from ..device import DeviceArray, _compared_as, _dtype_of
 
 __all__ = ["mean", "excprob", "products", "EnsembleProducts"]
 
@@ -38,33 +39,9 @@ MAX_THRESHOLDS = 16  # csrc/ensstats.hip kEnsMaxThr: thresholds per pass over th
 _NATIVE = (np.dtype(np.float32), np.dtype(np.float64))
 
 
-def _reference():
-    try:
-        from pysteps.postprocessing import ensemblestats as ref  # noqa: PLC0415
-    except ImportError:
-        return None
-    return None if ref.mean is mean else ref
-
-
-def _delegate(name, X, why, *args, **kwargs):
-    ref = _reference()
-    if ref is None or isinstance(X, DeviceArray):
-        raise NotImplementedError("pysteps_amd ensemblestats.%s: %s is not implemented on the device%s"
-                                  % (name, why, "" if ref is not None else " and pysteps is not importable"))
-    warnings.warn("pysteps_amd ensemblestats.%s: %s - running the reference's function" % (name, why), stacklevel=3)
-    return getattr(ref, name)(X, *args, **kwargs)
-
-
-def _compared_as(x, dtype):
-    """The float64 number that decides ``X >= x`` / ``X < x`` for a stack of ``dtype`` as NumPy evaluates it."""
-    if dtype == np.float32 and np.result_type(np.float32, x) == np.float32:
-        with np.errstate(over="ignore"):
-            return float(np.float32(x))
-    return float(x)
-
-
-def _dtype_of(X):
-    return X.dtype if isinstance(X, DeviceArray) else np.asanyarray(X).dtype
+def _stock(name):
+    """The reference's ``mean`` / ``excprob``, or None when pysteps is not importable."""
+    return lookup("postprocessing.ensemblestats", name, globals()[name])
 
 
 def _stack(X, k, plane_shape):
@@ -134,9 +111,10 @@ def mean(X, ignore_nan=False, X_thr=None):
     documented in the reference (ensemblestats.py:20-39).  ``ignore_nan`` ignores NaN, ``X_thr`` also values below it."""
     shape = _check_mean(X)
     dtype = _dtype_of(X)
-    if dtype not in _NATIVE:
-        return _delegate("mean", X, "dtype %s" % dtype, ignore_nan=ignore_nan, X_thr=X_thr)
     resident = isinstance(X, DeviceArray)
+    if dtype not in _NATIVE:
+        return decline("ensemblestats.mean", "dtype %s" % dtype, _stock("mean"), resident, UserWarning)(
+            X, ignore_nan=ignore_nan, X_thr=X_thr)
     thr = None if X_thr is None else _compared_as(X_thr, dtype)
     out, _ = _run(_stack(X, shape[0], shape[1:]), shape[0], shape[1:], [], False, True, ignore_nan, thr, False)
     return out if resident else out.to_host()
@@ -147,9 +125,10 @@ def excprob(X, X_thr, ignore_nan=False):
     ``(len(X_thr), m, n, ...)``, without the first axis for a scalar threshold (ensemblestats.py:61-115)."""
     shape = _check_excprob(X)
     dtype = _dtype_of(X)
-    if dtype not in _NATIVE:
-        return _delegate("excprob", X, "dtype %s" % dtype, X_thr, ignore_nan=ignore_nan)
     resident = isinstance(X, DeviceArray)
+    if dtype not in _NATIVE:
+        return decline("ensemblestats.excprob", "dtype %s" % dtype, _stock("excprob"), resident, UserWarning)(
+            X, X_thr, ignore_nan=ignore_nan)
     thresholds, scalar = _threshold_list(X_thr)
     if not thresholds:
         return np.stack([])  # the reference's own ValueError for an empty list
@@ -175,11 +154,11 @@ def _products(X, thresholds, mean, ignore_nan, mean_ignore_nan, mean_thr, _widen
         _check_mean(X)
     dtype = _dtype_of(X)
     if dtype not in _NATIVE:
-        ref = _reference()
-        if ref is None or isinstance(X, DeviceArray):
+        ref_mean, ref_excprob = _stock("mean"), _stock("excprob")
+        if ref_mean is None or ref_excprob is None or isinstance(X, DeviceArray):
             raise NotImplementedError("pysteps_amd ensemblestats.products: dtype %s is not implemented on the device" % dtype)
         warnings.warn("pysteps_amd ensemblestats.products: dtype %s - running the reference's functions" % dtype, stacklevel=3)
-        return (ref.mean(X, mean_ignore_nan, mean_thr) if want_mean else None), ref.excprob(X, thresholds, ignore_nan)
+        return (ref_mean(X, mean_ignore_nan, mean_thr) if want_mean else None), ref_excprob(X, thresholds, ignore_nan)
     resident = isinstance(X, DeviceArray)
     thr_list, scalar = _threshold_list(thresholds)
     if not thr_list and not want_mean:

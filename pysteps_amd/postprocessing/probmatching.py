@@ -18,22 +18,16 @@ with the reference as multisets per tie group, everything else bit for bit.
 import numpy as np
 
 from .. import _lib
+from .._reference import require
 from ..device import DeviceArray
 
 MIN_HOST_SIZE = 4096  # host arrays below this many pixels: two NumPy sorts beat the launch chain + transfers
 
-_reference_fn = None  # set by register.patch_probmatching(): the function this module replaced
 
 
-def _reference():
-    if _reference_fn is not None:
-        return _reference_fn
-    from pysteps.postprocessing import probmatching as ref_mod  # noqa: PLC0415
-
-    fn = getattr(ref_mod, "_reference_nonparam_match_empirical_cdf", ref_mod.nonparam_match_empirical_cdf)
-    if fn is nonparam_match_empirical_cdf:
-        raise NotImplementedError("the reference's nonparam_match_empirical_cdf is not reachable")
-    return fn
+def _stock():
+    """The reference's function: its ImportError without pysteps, NotImplementedError if ours has taken its place."""
+    return require("postprocessing.probmatching", "nonparam_match_empirical_cdf", nonparam_match_empirical_cdf)
 
 
 def nonparam_match_empirical_cdf(initial_array, target_array, ignore_indices=None):
@@ -44,7 +38,7 @@ def nonparam_match_empirical_cdf(initial_array, target_array, ignore_indices=Non
     if ignore_indices is not None:
         if resident or isinstance(initial_array, DeviceArray) or isinstance(target_array, DeviceArray):
             raise NotImplementedError("ignore_indices is not available for device-resident arrays")
-        return _reference()(initial_array, target_array, ignore_indices=ignore_indices)
+        return _stock()(initial_array, target_array, ignore_indices=ignore_indices)
     if not resident:
         if isinstance(initial_array, DeviceArray):
             initial_array = initial_array.to_host()
@@ -58,10 +52,10 @@ def nonparam_match_empirical_cdf(initial_array, target_array, ignore_indices=Non
             f"initial_array.shape={initial_array.shape}, target_array.shape={target_array.shape}"
         )
     if initial_array.size == 0:
-        return _reference()(initial_array, target_array)  # numpy's own error for empty reductions
+        return _stock()(initial_array, target_array)  # numpy's own error for empty reductions
     if not resident and initial_array.size < MIN_HOST_SIZE:
         try:  # small windows (nowcasts/sseps.py:783): the reference is faster; without pysteps, the device
-            return _reference()(initial_array, target_array)
+            return _stock()(initial_array, target_array)
         except (ImportError, NotImplementedError):
             pass
     if resident:
@@ -74,11 +68,11 @@ def nonparam_match_empirical_cdf(initial_array, target_array, ignore_indices=Non
     out = DeviceArray(initial_array.shape, np.float64)
     rc = _lib.lib().psh_probmatch_dev(d_init.ptr, d_trg.ptr, initial_array.size, out.ptr)
     if rc == _lib.PSH_EUNSUPPORTED and not resident:
-        return _reference()(initial_array, target_array)
+        return _stock()(initial_array, target_array)
     if rc == _lib.PSH_EUNSUPPORTED:
         # resident arrays the bucket pass declines (more than 16384 tied or bucket-sharing wet values,
         # infinities in the target): this one call crosses the bus, the member loop keeps going
-        got = _reference()(initial_array.to_host(), target_array.to_host())
+        got = _stock()(initial_array.to_host(), target_array.to_host())
         return DeviceArray.from_host(np.ascontiguousarray(got, dtype=np.float64))
     _lib.check(rc, "psh_probmatch_dev")
     return out if resident else out.to_host()

@@ -12,6 +12,8 @@ unchanged.  With ``override=True`` the stock names ("semilagrangian", "lk",
 pysteps/tests/test_interfaces.py:69-78,220-233 then fail by design).
 """
 
+from ._reference import patch, restore, swap, unpatch
+
 FFT_NAME = "hip"
 CASCADE_NAME = "fft_hip"  # pysteps.cascade.get_method("fft_hip") -> (decomposition_fft, recompose_fft)
 NOISE_NAMES = {"parametric_hip": "parametric", "nonparametric_hip": "nonparametric"}
@@ -48,6 +50,19 @@ def register_into(motion_methods, extrapolation_methods, override=False):
 # pysteps modules that bind the generic nowcast loop by name (``from pysteps.nowcasts.utils import
 # nowcast_main_loop``): steps.py:26, sprog.py, anvil.py, linda.py
 _MAIN_LOOP_USERS = ("steps", "sprog", "anvil", "linda")
+
+
+def _main_loop_users():
+    """``(name, module)`` of the nowcast modules that import and bind the loop."""
+    import importlib  # noqa: PLC0415
+
+    for name in _MAIN_LOOP_USERS:
+        try:
+            mod = importlib.import_module("pysteps.nowcasts." + name)
+        except Exception:
+            continue  # optional dependencies of that nowcast module are missing
+        if hasattr(mod, "nowcast_main_loop"):
+            yield name, mod
 
 
 def _hip_aware_get_method(reference_get_method):
@@ -148,258 +163,97 @@ def unregister_fft():
         utils_pkg.get_method = ref
 
 
+# The swaps of module attributes.  ``_reference.SWAPS`` lists, per key, the functions that change and why it is the
+# attribute - no method table - that has to change; the stock function stays reachable as ``_reference_<name>`` on the
+# reference's module, and inputs the device path declines are handed to it.
+
+
 def patch_probmatching():
-    """Replace ``pysteps.postprocessing.probmatching.nonparam_match_empirical_cdf`` by the device
-    version.  The member loops reach it through the module attribute
-    (``probmatching.nonparam_match_empirical_cdf(...)``: nowcasts/steps.py:1199, sprog.py:421,
-    sseps.py:783,804, blending/steps.py:3333) and there is no method table for it, so the attribute is
-    what has to change; the reference function stays reachable (calls with ``ignore_indices`` and
-    inputs the device path declines are handed to it)."""
-    import pysteps.postprocessing.probmatching as ref_mod  # noqa: PLC0415
-
-    from .postprocessing import probmatching as hip_mod  # noqa: PLC0415
-
-    if ref_mod.nonparam_match_empirical_cdf is hip_mod.nonparam_match_empirical_cdf:
-        return []
-    ref_mod._reference_nonparam_match_empirical_cdf = ref_mod.nonparam_match_empirical_cdf
-    hip_mod._reference_fn = ref_mod.nonparam_match_empirical_cdf
-    ref_mod.nonparam_match_empirical_cdf = hip_mod.nonparam_match_empirical_cdf
-    return ["probmatching:nonparam_match_empirical_cdf"]
+    """Replace ``pysteps.postprocessing.probmatching.nonparam_match_empirical_cdf`` by the device version."""
+    return patch("probmatching")
 
 
 def unpatch_probmatching():
     """Undo :func:`patch_probmatching`."""
-    import pysteps.postprocessing.probmatching as ref_mod  # noqa: PLC0415
-
-    ref = getattr(ref_mod, "_reference_nonparam_match_empirical_cdf", None)
-    if ref is not None:
-        ref_mod.nonparam_match_empirical_cdf = ref
-        del ref_mod._reference_nonparam_match_empirical_cdf
+    unpatch("probmatching")
 
 
 def patch_autoregression():
-    """Replace ``pysteps.timeseries.autoregression.iterate_ar_model`` (reached through the module
-    attribute: nowcasts/steps.py:1095,1137, sprog.py:398, sseps.py:678,749, anvil.py:483) by the device
-    version; series it does not take run the reference's function."""
-    import pysteps.timeseries.autoregression as ref_mod  # noqa: PLC0415
-
-    from .timeseries import autoregression as hip_mod  # noqa: PLC0415
-
-    if ref_mod.iterate_ar_model is hip_mod.iterate_ar_model:
-        return []
-    ref_mod._reference_iterate_ar_model = ref_mod.iterate_ar_model
-    hip_mod._reference_fn = ref_mod.iterate_ar_model
-    ref_mod.iterate_ar_model = hip_mod.iterate_ar_model
-    return ["autoregression:iterate_ar_model"]
+    """Replace ``pysteps.timeseries.autoregression.iterate_ar_model`` by the device version."""
+    return patch("autoregression")
 
 
 def unpatch_autoregression():
     """Undo :func:`patch_autoregression`."""
-    import pysteps.timeseries.autoregression as ref_mod  # noqa: PLC0415
-
-    ref = getattr(ref_mod, "_reference_iterate_ar_model", None)
-    if ref is not None:
-        ref_mod.iterate_ar_model = ref
-        del ref_mod._reference_iterate_ar_model
+    unpatch("autoregression")
 
 
 def patch_dilated_mask():
-    """Replace ``pysteps.nowcasts.utils.compute_dilated_mask`` (the incremental precipitation mask,
-    reached as ``nowcast_utils.compute_dilated_mask(...)``: nowcasts/steps.py:983,1210, sseps.py:472,821)
-    by the device version; masks it does not take run the reference's function."""
-    import pysteps.nowcasts.utils as ref_mod  # noqa: PLC0415
-
-    from .nowcasts import utils as hip_mod  # noqa: PLC0415
-
-    if ref_mod.compute_dilated_mask is hip_mod.compute_dilated_mask:
-        return []
-    ref_mod._reference_compute_dilated_mask = ref_mod.compute_dilated_mask
-    hip_mod._reference_dilated_mask = ref_mod.compute_dilated_mask
-    ref_mod.compute_dilated_mask = hip_mod.compute_dilated_mask
-    return ["nowcasts.utils:compute_dilated_mask"]
+    """Replace ``pysteps.nowcasts.utils.compute_dilated_mask`` by the device version."""
+    return patch("dilated_mask")
 
 
 def unpatch_dilated_mask():
     """Undo :func:`patch_dilated_mask`."""
-    import pysteps.nowcasts.utils as ref_mod  # noqa: PLC0415
-
-    ref = getattr(ref_mod, "_reference_compute_dilated_mask", None)
-    if ref is not None:
-        ref_mod.compute_dilated_mask = ref
-        del ref_mod._reference_compute_dilated_mask
+    unpatch("dilated_mask")
 
 
 def patch_fss():
     """Replace ``fss`` and ``fss_accum`` of ``pysteps.verification.spatialscores`` by the device versions
-    (:mod:`pysteps_amd.verification.spatialscores`).  ``pysteps.verification.interface.get_method`` is an if-chain that
-    imports ``fss`` from that module when it is called (interface.py:169), so there is no table to add a name to and the
-    attributes are what has to change; ``get_method("fss")`` and the reference's own ``fss`` (which calls the module's
-    ``fss_accum``) then count on the device.  Inputs the device path declines run the reference's ``fss_accum``."""
-    import pysteps.verification.spatialscores as ref_mod  # noqa: PLC0415
-
-    from .verification import spatialscores as hip_mod  # noqa: PLC0415
-
-    if ref_mod.fss_accum is hip_mod.fss_accum:
-        return []
-    ref_mod._reference_fss, ref_mod._reference_fss_accum = ref_mod.fss, ref_mod.fss_accum
-    hip_mod._reference_fss_accum = ref_mod.fss_accum
-    ref_mod.fss, ref_mod.fss_accum = hip_mod.fss, hip_mod.fss_accum
-    return ["verification:fss", "verification:fss_accum"]
+    (:mod:`pysteps_amd.verification.spatialscores`): ``get_method("fss")`` and the reference's own ``fss`` then count on
+    the device."""
+    return patch("fss")
 
 
 def unpatch_fss():
     """Undo :func:`patch_fss`."""
-    import pysteps.verification.spatialscores as ref_mod  # noqa: PLC0415
-
-    from .verification import spatialscores as hip_mod  # noqa: PLC0415
-
-    if getattr(ref_mod, "_reference_fss_accum", None) is not None:
-        ref_mod.fss, ref_mod.fss_accum = ref_mod._reference_fss, ref_mod._reference_fss_accum
-        del ref_mod._reference_fss, ref_mod._reference_fss_accum
-    hip_mod._reference_fss_accum = None
+    unpatch("fss")
 
 
 def patch_detscores():
     """Replace ``det_cat_fct`` and ``det_cat_fct_accum`` of ``pysteps.verification.detcatscores`` and ``det_cont_fct`` and
     ``det_cont_fct_accum`` of ``pysteps.verification.detcontscores`` by the device versions
-    (:mod:`pysteps_amd.verification.detcatscores`, :mod:`pysteps_amd.verification.detcontscores`).
-    ``pysteps.verification.interface.get_method`` imports the two ``_fct`` functions from their modules when it is
-    called (interface.py:167-168) and there is no table to add a name to, so the attributes are what has to change.
-    Inputs the device path declines, and the offline scores, run the reference's functions, which stay reachable."""
-    import pysteps.verification.detcatscores as ref_cat  # noqa: PLC0415
-    import pysteps.verification.detcontscores as ref_cont  # noqa: PLC0415
-
-    from .verification import detcatscores as hip_cat  # noqa: PLC0415
-    from .verification import detcontscores as hip_cont  # noqa: PLC0415
-
-    added = []
-    for ref_mod, hip_mod, stem in ((ref_cat, hip_cat, "det_cat_fct"), (ref_cont, hip_cont, "det_cont_fct")):
-        if getattr(ref_mod, stem + "_accum") is getattr(hip_mod, stem + "_accum"):
-            continue
-        for name, holder in ((stem, "_reference_fct"), (stem + "_accum", "_reference_fct_accum")):
-            setattr(ref_mod, "_reference_" + name, getattr(ref_mod, name))
-            setattr(hip_mod, holder, getattr(ref_mod, name))
-            setattr(ref_mod, name, getattr(hip_mod, name))
-            added.append("verification:" + name)
-    return added
+    (:mod:`pysteps_amd.verification.detcatscores`, :mod:`pysteps_amd.verification.detcontscores`)."""
+    return patch("detscores")
 
 
 def unpatch_detscores():
     """Undo :func:`patch_detscores`."""
-    import pysteps.verification.detcatscores as ref_cat  # noqa: PLC0415
-    import pysteps.verification.detcontscores as ref_cont  # noqa: PLC0415
-
-    from .verification import detcatscores as hip_cat  # noqa: PLC0415
-    from .verification import detcontscores as hip_cont  # noqa: PLC0415
-
-    for ref_mod, hip_mod, stem in ((ref_cat, hip_cat, "det_cat_fct"), (ref_cont, hip_cont, "det_cont_fct")):
-        for name in (stem, stem + "_accum"):
-            ref = getattr(ref_mod, "_reference_" + name, None)
-            if ref is not None:
-                setattr(ref_mod, name, ref)
-                delattr(ref_mod, "_reference_" + name)
-        hip_mod._reference_fct = hip_mod._reference_fct_accum = None
+    unpatch("detscores")
 
 
 def patch_probscores():
     """Replace ``CRPS``, ``reldiag`` and ``ROC_curve`` and their ``_accum`` functions in
-    ``pysteps.verification.probscores`` by the device versions (:mod:`pysteps_amd.verification.probscores`).
-    ``pysteps.verification.interface.get_method`` imports the three one-shot functions from that module when it is
-    called (interface.py:239) and there is no table to add a name to, so the attributes are what has to change.  The
-    ``_init`` and ``_compute`` functions stay the reference's: objects of either side are interchangeable.  Inputs the
-    device path declines run the reference's ``_accum`` functions, which stay reachable."""
-    import pysteps.verification.probscores as ref_mod  # noqa: PLC0415
-
-    from .verification import probscores as hip_mod  # noqa: PLC0415
-
-    if ref_mod.CRPS_accum is hip_mod.CRPS_accum:
-        return []
-    added = []
-    for name in hip_mod.SWAPPED:
-        setattr(ref_mod, "_reference_" + name, getattr(ref_mod, name))
-        hip_mod._held[name] = getattr(ref_mod, name)
-        setattr(ref_mod, name, getattr(hip_mod, name))
-        added.append("verification:" + name)
-    return added
+    ``pysteps.verification.probscores`` by the device versions (:mod:`pysteps_amd.verification.probscores`)."""
+    return patch("probscores")
 
 
 def unpatch_probscores():
     """Undo :func:`patch_probscores`."""
-    import pysteps.verification.probscores as ref_mod  # noqa: PLC0415
-
-    from .verification import probscores as hip_mod  # noqa: PLC0415
-
-    for name in hip_mod.SWAPPED:
-        ref = getattr(ref_mod, "_reference_" + name, None)
-        if ref is not None:
-            setattr(ref_mod, name, ref)
-            delattr(ref_mod, "_reference_" + name)
-    hip_mod._held.clear()
+    unpatch("probscores")
 
 
 def patch_noise_stddev_adj():
     """Replace ``pysteps.noise.utils.compute_noise_stddev_adjs`` by the device version
-    (:mod:`pysteps_amd.noise.utils`).  ``nowcasts.steps`` with ``noise_stddev_adj="auto"`` looks the function up as
-    ``noise.utils.compute_noise_stddev_adjs`` when it is called (nowcasts/steps.py:760) and there is no method table
-    for it, so the module attribute is what has to change; calls the device path declines run the reference's
-    function with a ``RuntimeWarning``."""
-    import pysteps.noise.utils as ref_mod  # noqa: PLC0415
-
-    from .noise import utils as hip_mod  # noqa: PLC0415
-
-    if ref_mod.compute_noise_stddev_adjs is hip_mod.compute_noise_stddev_adjs:
-        return []
-    ref_mod._reference_compute_noise_stddev_adjs = ref_mod.compute_noise_stddev_adjs
-    hip_mod._reference_fn = ref_mod.compute_noise_stddev_adjs
-    ref_mod.compute_noise_stddev_adjs = hip_mod.compute_noise_stddev_adjs
-    return ["noise.utils:compute_noise_stddev_adjs"]
+    (:mod:`pysteps_amd.noise.utils`); calls the device path declines run the reference's function with a
+    ``RuntimeWarning``."""
+    return patch("noise_stddev_adj")
 
 
 def unpatch_noise_stddev_adj():
     """Undo :func:`patch_noise_stddev_adj`."""
-    import pysteps.noise.utils as ref_mod  # noqa: PLC0415
-
-    from .noise import utils as hip_mod  # noqa: PLC0415
-
-    ref = getattr(ref_mod, "_reference_compute_noise_stddev_adjs", None)
-    if ref is not None:
-        ref_mod.compute_noise_stddev_adjs = ref
-        del ref_mod._reference_compute_noise_stddev_adjs
-    hip_mod._reference_fn = None
+    unpatch("noise_stddev_adj")
 
 
 def patch_rapsd():
-    """Replace ``pysteps.utils.spectral.rapsd`` by the device version (:mod:`pysteps_amd.utils.spectral`).
-    ``pysteps.utils.interface.get_method("rapsd")`` builds its table from ``spectral.rapsd`` when it is called and
-    ``noise.fftgenerators.initialize_param_2d_fft_filter`` calls ``utils.spectral.rapsd`` (fftgenerators.py:150), so both
-    go through the device after the swap; inputs the device path declines run the reference's function with a
-    ``RuntimeWarning``.  The reference's ``downscaling.rainfarm`` binds the name when it is imported (``from
-    ..utils.spectral import rapsd``), uses it for spectral fusion alone and keeps the reference's function; the device
-    RainFARM (``"rainfarm_hip"``, :func:`register_downscaling`) hands spectral fusion to the reference and needs no
-    ``rapsd``."""
-    import pysteps.utils.spectral as ref_mod  # noqa: PLC0415
-
-    from .utils import spectral as hip_mod  # noqa: PLC0415
-
-    if ref_mod.rapsd is hip_mod.rapsd:
-        return []
-    ref_mod._reference_rapsd = ref_mod.rapsd
-    hip_mod._reference_rapsd = ref_mod.rapsd
-    ref_mod.rapsd = hip_mod.rapsd
-    return ["utils.spectral:rapsd"]
+    """Replace ``pysteps.utils.spectral.rapsd`` by the device version (:mod:`pysteps_amd.utils.spectral`); inputs the
+    device path declines run the reference's function with a ``RuntimeWarning``."""
+    return patch("rapsd")
 
 
 def unpatch_rapsd():
     """Undo :func:`patch_rapsd`."""
-    import pysteps.utils.spectral as ref_mod  # noqa: PLC0415
-
-    from .utils import spectral as hip_mod  # noqa: PLC0415
-
-    ref = getattr(ref_mod, "_reference_rapsd", None)
-    if ref is not None:
-        ref_mod.rapsd = ref
-        del ref_mod._reference_rapsd
-    hip_mod._reference_rapsd = None
+    unpatch("rapsd")
 
 
 def register_nowcasts():
@@ -494,50 +348,21 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     if fft:
         added += register_fft()
         added += register_spectral()
-    if probmatching:
-        added += patch_probmatching()
-    if autoregression:
-        added += patch_autoregression()
-    if dilated_mask:
-        added += patch_dilated_mask()
-    if fss:
-        added += patch_fss()
-    if noise_stddev_adj:
-        added += patch_noise_stddev_adj()
-    if detscores:
-        added += patch_detscores()
-    if rapsd:
-        added += patch_rapsd()
-    if probscores:
-        added += patch_probscores()
+    for key, wanted in (("probmatching", probmatching), ("autoregression", autoregression), ("dilated_mask", dilated_mask),
+                        ("fss", fss), ("noise_stddev_adj", noise_stddev_adj), ("detscores", detscores), ("rapsd", rapsd),
+                        ("probscores", probscores)):
+        if wanted:
+            added += patch(key)
     if patch_main_loop:
-        import importlib  # noqa: PLC0415
-
         from .nowcasts.utils import nowcast_main_loop  # noqa: PLC0415
 
-        for name in _MAIN_LOOP_USERS:
-            try:
-                mod = importlib.import_module("pysteps.nowcasts." + name)
-            except Exception:
-                continue  # optional dependencies of that nowcast module are missing
-            if hasattr(mod, "nowcast_main_loop"):
-                if not hasattr(mod, "_reference_nowcast_main_loop"):
-                    mod._reference_nowcast_main_loop = mod.nowcast_main_loop
-                mod.nowcast_main_loop = nowcast_main_loop
-                added.append("main_loop:" + name)
+        for name, mod in _main_loop_users():
+            swap(mod, "nowcast_main_loop", nowcast_main_loop)
+            added.append("main_loop:" + name)
     return added
 
 
 def unpatch_main_loop():
     """Undo ``register(patch_main_loop=True)``."""
-    import importlib  # noqa: PLC0415
-
-    for name in _MAIN_LOOP_USERS:
-        try:
-            mod = importlib.import_module("pysteps.nowcasts." + name)
-        except Exception:
-            continue
-        ref = getattr(mod, "_reference_nowcast_main_loop", None)
-        if ref is not None:
-            mod.nowcast_main_loop = ref
-            del mod._reference_nowcast_main_loop
+    for _, mod in _main_loop_users():
+        restore(mod, "nowcast_main_loop")

@@ -17,23 +17,17 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from .._reference import require
 from ..device import DeviceArray
 
 MAX_ORDER = 8
 MIN_HOST_PLANE = 1 << 16  # host arrays below this many values per field stay with NumPy
 
-_reference_fn = None  # set by register.patch_autoregression(): the function this module replaced
 
 
-def _reference():
-    if _reference_fn is not None:
-        return _reference_fn
-    from pysteps.timeseries import autoregression as ref_mod  # noqa: PLC0415
-
-    fn = getattr(ref_mod, "_reference_iterate_ar_model", ref_mod.iterate_ar_model)
-    if fn is iterate_ar_model:
-        raise NotImplementedError("the reference's iterate_ar_model is not reachable")
-    return fn
+def _stock():
+    """The reference's function: its ImportError without pysteps, NotImplementedError if ours has taken its place."""
+    return require("timeseries.autoregression", "iterate_ar_model", iterate_ar_model)
 
 
 def _scalar_phi(phi):
@@ -60,7 +54,7 @@ def iterate_ar_model(x, phi, eps=None):
         if not eligible or (eps is not None and not isinstance(eps, DeviceArray)):
             raise NotImplementedError("device-resident series: float64, scalar phi of order 1..8, resident eps")
     elif not eligible or isinstance(eps, DeviceArray) or int(np.prod(x.shape[1:])) < MIN_HOST_PLANE:
-        return _reference()(x, phi, eps=eps)
+        return _stock()(x, phi, eps=eps)
     if x.shape[0] < len(phi) - 1:  # autoregression.py:1041-1045
         raise ValueError(
             "dimension mismatch between x and phi: x.shape[0]=%d, len(phi)=%d" % (x.shape[0], len(phi))
@@ -72,7 +66,7 @@ def iterate_ar_model(x, phi, eps=None):
         )
     plane = int(np.prod(x.shape[1:]))
     if plane == 0:
-        return _reference()(x, phi, eps=eps)
+        return _stock()(x, phi, eps=eps)
     d_x = x if resident else DeviceArray.from_host(x, np.float64, sync=False)
     d_eps = eps if resident or eps is None else DeviceArray.from_host(eps, np.float64, sync=False)
     out = DeviceArray(x.shape, np.float64)

@@ -12,17 +12,16 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray
 
 __all__ = ["check_norain"]
 
 
 def _window(m, n, win_fun):
-    try:
-        from pysteps.utils.tapering import compute_window_function  # noqa: PLC0415
-    except Exception as exc:
-        raise NotImplementedError(
-            "check_norain: win_fun=%r needs pysteps.utils.tapering, which is not importable" % (win_fun,)) from exc
+    compute_window_function = lookup("utils.tapering", "compute_window_function", None)
+    if compute_window_function is None:
+        raise NotImplementedError("check_norain: win_fun=%r needs pysteps.utils.tapering, which is not importable" % (win_fun,))
     return compute_window_function(m, n, win_fun)
 
 

@@ -17,17 +17,10 @@ import warnings
 import numpy as np
 
 from .. import _lib
+from .._reference import lookup
 from ..device import DeviceArray
 
 __all__ = ["idwinterp2d", "rbfinterp2d"]
-
-
-def _reference_idw():
-    try:
-        from pysteps.utils.interpolate import idwinterp2d as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is idwinterp2d else ref
 
 
 def _regular_axis(grid, name):
@@ -122,7 +115,7 @@ def idwinterp2d(xy_coord, values, xgrid, ygrid, power=0.5, k=20, dist_offset=0.5
     elif not power > 0:
         why = "power=%r (the kernel needs power > 0)" % (power,)
     if why is not None:  # outside the kernel's limits: the reference takes the call
-        ref = _reference_idw()
+        ref = lookup("utils.interpolate", "idwinterp2d", idwinterp2d)
         if ref is None:
             raise NotImplementedError(
                 "pysteps_amd idwinterp2d: %s is not implemented on the HIP path and pysteps is not importable" % why
@@ -151,14 +144,6 @@ def idwinterp2d(xy_coord, values, xgrid, ygrid, power=0.5, k=20, dist_offset=0.5
 
 
 _RBF_FUNCTIONS = {"multiquadric": 0, "inverse": 1, "gaussian": 2, "linear": 3, "cubic": 4, "quintic": 5, "thin_plate": 6}
-
-
-def _reference_rbf():
-    try:
-        from pysteps.utils.interpolate import rbfinterp2d as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref is rbfinterp2d else ref
 
 
 def rbfinterp2d(xy_coord, values, xgrid, ygrid, **kwargs):
@@ -195,7 +180,7 @@ def rbfinterp2d(xy_coord, values, xgrid, ygrid, **kwargs):
     why = None
     if ax is None or ay is None or xy_coord.shape[1] != 2:
         why = "irregular grid or coordinates that are not 2-d"
-    elif values.ndim == 1 and _reference_rbf() is not None:
+    elif values.ndim == 1 and lookup("utils.interpolate", "rbfinterp2d", rbfinterp2d) is not None:
         # (the reference moves the LAST axis of the Rbf result to the front, interpolate.py:169 - for 1-d values
         # that is a transposition, per grid chunk, and an error on non-square chunks: its behaviour there is its own)
         why = "1-d values (the reference's own axis handling applies)"
@@ -206,7 +191,7 @@ def rbfinterp2d(xy_coord, values, xgrid, ygrid, **kwargs):
     elif any(k not in ("function", "epsilon", "smooth", "norm", "mode", "rbfunction", "k") for k in rbf_kwargs):
         why = "keyword arguments %r" % sorted(rbf_kwargs)
     if why is not None:  # outside the kernel's limits: the reference takes the call
-        ref = _reference_rbf()
+        ref = lookup("utils.interpolate", "rbfinterp2d", rbfinterp2d)
         if ref is None:
             raise NotImplementedError(
                 "pysteps_amd rbfinterp2d: %s is not implemented on the HIP path and pysteps is not importable" % why

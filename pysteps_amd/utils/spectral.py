@@ -21,26 +21,13 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from .._reference import decline, lookup
 from ..device import DeviceArray
-from ..verification.detcatscores import _decline
 from . import fft as hip_fft
 
 __all__ = ["rapsd", "rapsd_table", "rapsd_counts", "RapsdAccumulator"]
 
-# the reference's rapsd while register.patch_rapsd() has replaced it
-_reference_rapsd = None
 _BATCH_BYTES = 1 << 30  # half spectra held at a time by the transform path
-
-
-def _reference():
-    """The reference's ``rapsd``, or None when pysteps is not importable."""
-    if _reference_rapsd is not None:
-        return _reference_rapsd
-    try:
-        from pysteps.utils import spectral as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref.rapsd is rapsd else ref.rapsd
 
 
 def _bins(m, n):
@@ -169,8 +156,8 @@ def rapsd(field, fft_method=None, return_freq=False, d=1.0, normalize=False, **f
     if why is not None:
         # the reference calls fft_method.fft2 / .fftshift: the string "hip" stands for its default method there
         method = np.fft if isinstance(fft_method, str) else fft_method
-        return _decline("rapsd", why, _reference(), resident)(field, fft_method=method, return_freq=return_freq, d=d,
-                                                              normalize=normalize, **fft_kwargs)
+        return decline("rapsd", why, lookup("utils.spectral", "rapsd", rapsd), resident)(
+            field, fft_method=method, return_freq=return_freq, d=d, normalize=normalize, **fft_kwargs)
     result = result[0]
     if normalize:
         result /= np.sum(result)
@@ -196,7 +183,7 @@ def rapsd_table(fields, fft_method="hip", normalize=False, return_freq=False, d=
     table = _spectra(fields, fft_method, {}) if why is None else None
     if table is None:
         if resident:
-            _decline("rapsd_table", why or "an infinite value", _reference(), True)
+            decline("rapsd_table", why or "an infinite value", lookup("utils.spectral", "rapsd", rapsd), True)
         table = np.stack([rapsd(fields[k], fft_method=fft_method) for k in range(K)])  # declines plane by plane
     if normalize:
         for k in range(K):

@@ -16,53 +16,24 @@ handful of numbers, restated operation by operation, so a table holds the refere
 
 Served on the device: ``axis=None`` (all elements) and, for ``(K, m, n)`` fields, the two trailing axes (``axis=(1, 2)``
 or ``(2, 1)``), float32 or float64 on either side.  A threshold meets each field as NumPy compares it
-(``postprocessing/ensemblestats.py::_compared_as``).  Any other axis - the negative ones too, which in the reference
+(``device.py::_compared_as``).  Any other axis - the negative ones too, which in the reference
 mean "no integration" - and any other dtype goes to the reference's function with a ``RuntimeWarning`` when pysteps is
 importable and the fields are NumPy arrays, and raises ``NotImplementedError`` otherwise.
 """
 
 import collections.abc
 import ctypes
-import warnings
 
 import numpy as np
 
 from .. import _lib
-from ..device import DeviceArray
-from ..postprocessing.ensemblestats import _compared_as
+from .._reference import decline, lookup
+from ..device import DeviceArray, _compared_as, _dtype_of, _upload
 
 __all__ = ["det_cat_fct", "det_cat_fct_init", "det_cat_fct_accum", "det_cat_fct_merge", "det_cat_fct_compute", "det_cat_table"]
 
 _NATIVE = (np.dtype(np.float32), np.dtype(np.float64))
 _COUNT_KEYS = ("hits", "misses", "false_alarms", "correct_negatives")  # the order of the kernel's four counts
-# the reference's det_cat_fct / det_cat_fct_accum while register.patch_detscores() has replaced them
-_reference_fct = None
-_reference_fct_accum = None
-
-
-def _reference(name):
-    """The reference's function ``name`` of pysteps.verification.detcatscores, or None when pysteps is not importable."""
-    held = {"det_cat_fct": _reference_fct, "det_cat_fct_accum": _reference_fct_accum}[name]
-    if held is not None:
-        return held
-    try:
-        from pysteps.verification import detcatscores as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    fn = getattr(ref, name)
-    return None if fn is globals()[name] else fn
-
-
-def _dtype_of(X):
-    return X.dtype if isinstance(X, DeviceArray) else np.asanyarray(X).dtype
-
-
-def _upload(X):
-    if isinstance(X, DeviceArray):
-        return X
-    return DeviceArray.from_host(np.ascontiguousarray(np.asarray(X)), sync=False)
-
-
 def _as_iterable_axis(x):
     if x is None or (isinstance(x, collections.abc.Iterable) and not isinstance(x, int)):
         return x
@@ -108,15 +79,6 @@ def _layout(shape, axis, dtypes):
     return None, "axis %r (all elements, or the two trailing axes of (K, m, n) fields)" % (tuple(axis),)
 
 
-def _decline(name, why, reference, resident):
-    """Warn and return the reference's function for declined input, or raise when there is none to hand it to."""
-    if reference is None or resident:
-        raise NotImplementedError("pysteps_amd %s: %s is not implemented on the device%s"
-                                  % (name, why, "" if reference is not None else " and pysteps is not importable"))
-    warnings.warn("pysteps_amd %s: %s - running the reference's function" % (name, why), RuntimeWarning, stacklevel=3)
-    return reference
-
-
 def _counts(dev_f, dev_o, K, npix, shared, thr_f, thr_o):
     """uint64 ``(K, nthr, 4)`` of device fields: hits, misses, false alarms, correct negatives; thresholds are the
     float64 numbers to compare with."""
@@ -157,7 +119,8 @@ def det_cat_fct_accum(contab, pred, obs):
     dt_f, dt_o = _dtype_of(pred), _dtype_of(obs)
     layout, why = _layout(tuple(pred.shape), axis, (dt_f, dt_o))
     if why is not None:
-        return _decline("det_cat_fct_accum", why, _reference("det_cat_fct_accum"), resident)(contab, pred, obs)
+        return decline("det_cat_fct_accum", why, lookup("verification.detcatscores", "det_cat_fct_accum", det_cat_fct_accum),
+                       resident)(contab, pred, obs)
     K, npix, nshape = layout
     if contab["hits"] is None:
         for key in _COUNT_KEYS:

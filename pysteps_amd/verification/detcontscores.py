@@ -33,10 +33,9 @@ from fractions import Fraction
 import numpy as np
 
 from .. import _lib
-from ..device import DeviceArray
-from ..postprocessing.ensemblestats import _compared_as
-from .detcatscores import (_as_iterable_axis, _as_iterable_scores, _check_fields, _decline, _dtype_of, _layout, _table_fields,
-                           _upload)
+from .._reference import decline, lookup
+from ..device import DeviceArray, _compared_as, _dtype_of, _upload
+from .detcatscores import _as_iterable_axis, _as_iterable_scores, _check_fields, _layout, _table_fields
 
 __all__ = ["det_cont_fct", "det_cont_fct_init", "det_cont_fct_accum", "det_cont_fct_merge", "det_cont_fct_compute",
            "det_cont_table"]
@@ -46,22 +45,11 @@ _OFFLINE = ("scatter", "corr_s")
 # the kernel's sums (csrc/detscores.hip): over the pairs, then over each field's finite pixels
 _RES, _RES2, _ABS, _SUM2, _OBS_PAIR, _PRED_PAIR, _OBS_PRED, _OBS, _OBS2, _PRED, _PRED2 = range(11)
 _CONDITIONING = {None: 0, "single": 1, "double": 2}
-# the reference's det_cont_fct / det_cont_fct_accum while register.patch_detscores() has replaced them
-_reference_fct = None
-_reference_fct_accum = None
 
 
-def _reference(name):
+def _stock(name):
     """The reference's function ``name`` of pysteps.verification.detcontscores, or None when pysteps is not importable."""
-    held = {"det_cont_fct": _reference_fct, "det_cont_fct_accum": _reference_fct_accum}[name]
-    if held is not None:
-        return held
-    try:
-        from pysteps.verification import detcontscores as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    fn = getattr(ref, name)
-    return None if fn is globals()[name] else fn
+    return lookup("verification.detcontscores", name, globals()[name])
 
 
 def _conditioning_code(conditioning):
@@ -179,8 +167,8 @@ def det_cont_fct(pred, obs, scores="", axis=None, conditioning=None, thr=0.0):
     names = [name for name in ("corr_s", "scatter") if "" in offline or name in [str(s).lower() for s in offline]]
     if names:
         resident = isinstance(pred, DeviceArray) or isinstance(obs, DeviceArray)
-        ref = _decline("det_cont_fct", "the offline score%s %s" % ("s" if len(names) > 1 else "", " and ".join(names)),
-                       _reference("det_cont_fct"), resident)
+        ref = decline("det_cont_fct", "the offline score%s %s" % ("s" if len(names) > 1 else "", " and ".join(names)),
+                       _stock("det_cont_fct"), resident)
         result.update(ref(pred, obs, scores=names, axis=axis, conditioning=conditioning, thr=thr))
     return result
 
@@ -201,7 +189,7 @@ def det_cont_fct_accum(err, pred, obs):
     dt_f, dt_o = _dtype_of(pred), _dtype_of(obs)
     layout, why = _layout(tuple(pred.shape), axis, (dt_f, dt_o))
     if why is not None:
-        return _decline("det_cont_fct_accum", why, _reference("det_cont_fct_accum"), resident)(err, pred, obs)
+        return decline("det_cont_fct_accum", why, _stock("det_cont_fct_accum"), resident)(err, pred, obs)
     K, npix, nshape = layout
     if err["cov"] is not None and err["cov"].shape != nshape:
         raise ValueError("the shape of the input arrays does not match the shape of the verification object %s!=%s"
@@ -210,7 +198,7 @@ def det_cont_fct_accum(err, pred, obs):
     counts, sums = _sums(_upload(pred), _upload(obs), K, npix, False, code, _compared_as(err["thr"], dt_f),
                          _compared_as(err["thr"], dt_o))
     if counts[:, 3].any():
-        return _decline("det_cont_fct_accum", "an infinite value", _reference("det_cont_fct_accum"), resident)(err, pred, obs)
+        return decline("det_cont_fct_accum", "an infinite value", _stock("det_cont_fct_accum"), resident)(err, pred, obs)
     if err["cov"] is None:
         _zeros(err, nshape)
     batch, n = _batch(counts, sums, nshape)

@@ -18,7 +18,7 @@ What the reference's ``_accum`` functions add to their objects, as its code has 
 ``psh_probbins_dev`` serves the last two from one read; the object's own ``bin_edges`` and ``prob_thrs`` are compared
 as they are, so objects made by the reference's ``_init`` functions and by these are interchangeable.  ``X_min`` meets
 the observation and a probability threshold meets the probabilities as NumPy compares them
-(``postprocessing/ensemblestats.py::_compared_as``).  The ``_compute`` functions are host arithmetic on a handful of
+(``device.py::_compared_as``).  The ``_compute`` functions are host arithmetic on a handful of
 numbers, restated operation by operation.  The inputs are not modified.
 
 More than 64 members, more than 64 bins or probability thresholds, bin edges that do not increase and dtypes other
@@ -36,9 +36,9 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ..device import DeviceArray
-from ..postprocessing.ensemblestats import _compared_as
-from .detcatscores import _NATIVE, _decline, _dtype_of, _upload
+from .._reference import decline, lookup
+from ..device import DeviceArray, _compared_as, _dtype_of, _upload
+from .detcatscores import _NATIVE
 
 __all__ = ["CRPS", "CRPS_init", "CRPS_accum", "CRPS_compute", "reldiag", "reldiag_init", "reldiag_accum", "reldiag_compute",
            "ROC_curve", "ROC_curve_init", "ROC_curve_accum", "ROC_curve_compute", "crps_table", "crps_weights"]
@@ -46,20 +46,11 @@ __all__ = ["CRPS", "CRPS_init", "CRPS_accum", "CRPS_compute", "reldiag", "reldia
 MAX_MEMBERS = 64  # csrc/probscores.hip kCrpsMaxMembers
 MAX_BINS = 64  # kBinsLanes: bins and probability thresholds of one pass
 SWAPPED = ("CRPS", "CRPS_accum", "reldiag", "reldiag_accum", "ROC_curve", "ROC_curve_accum")
-# the reference's functions while register.patch_probscores() has replaced them
-_held = {}
 
 
-def _reference(name):
+def _stock(name):
     """The reference's function ``name`` of pysteps.verification.probscores, or None when pysteps is not importable."""
-    if name in _held:
-        return _held[name]
-    try:
-        from pysteps.verification import probscores as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    fn = getattr(ref, name)
-    return None if fn is globals()[name] else fn
+    return lookup("verification.probscores", name, globals()[name])
 
 
 def crps_weights(k):
@@ -142,7 +133,7 @@ def CRPS_accum(CRPS, X_f, X_o):  # noqa: N803 (the reference's parameter names)
         raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,) " % (npix, _size(shape_o)))
     why = _crps_declined(k, (_dtype_of(X_f), _dtype_of(X_o)))
     if why is not None:
-        return _decline("CRPS_accum", why, _reference("CRPS_accum"), resident)(CRPS, X_f, X_o)
+        return decline("CRPS_accum", why, _stock("CRPS_accum"), resident)(CRPS, X_f, X_o)
     if npix == 0:
         counts, sums = np.zeros(1, np.uint64), np.zeros((1, 2))
     else:
@@ -257,7 +248,7 @@ def reldiag_accum(reldiag, P_f, X_o):  # noqa: N803
     if why is None:
         edges, why = _edges_of(reldiag)
     if why is not None:
-        return _decline("reldiag_accum", why, _reference("reldiag_accum"), resident)(reldiag, P_f, X_o)
+        return decline("reldiag_accum", why, _stock("reldiag_accum"), resident)(reldiag, P_f, X_o)
     if npix == 0:
         bins, sums = np.zeros((edges.size - 1, 2), np.uint64), np.zeros((edges.size - 1, 2))
     else:
@@ -297,7 +288,7 @@ def ROC_curve_accum(ROC, P_f, X_o):  # noqa: N802, N803
     if why is None:
         thrs, why = _thresholds_of(ROC, dt_p)
     if why is not None:
-        return _decline("ROC_curve_accum", why, _reference("ROC_curve_accum"), resident)(ROC, P_f, X_o)
+        return decline("ROC_curve_accum", why, _stock("ROC_curve_accum"), resident)(ROC, P_f, X_o)
     if npix == 0 or thrs.size == 0:
         return None
     _, _, roc = _bins(_upload(P_f), _upload(X_o), npix, _compared_as(ROC["X_min"], dt_o), None, thrs)

@@ -16,7 +16,7 @@ the reference is then the side that carries the rounding error (tests/test_fss_c
 * :class:`FssAccumulator`: a nowcast ``callback`` that scores the members of every lead time where they lie.
 
 A threshold is compared as NumPy compares it: a Python number meets a float32 field as float32, a ``numpy.float64``
-scalar as float64 (``postprocessing/ensemblestats.py::_compared_as``).  What the device path does not take (another
+scalar as float64 (``device.py::_compared_as``).  What the device path does not take (another
 dtype, a scale that is not an integer or exceeds 255, a side above 65535 pixels, a threshold so large that
 ``thr - 1 == thr``) goes to the reference with a warning when pysteps is importable and raises ``NotImplementedError``
 otherwise.
@@ -28,8 +28,8 @@ import warnings
 import numpy as np
 
 from .. import _lib
-from ..device import DeviceArray
-from ..postprocessing.ensemblestats import _compared_as
+from .._reference import decline, lookup
+from ..device import DeviceArray, _compared_as, _dtype_of, _upload
 
 __all__ = ["fss", "fss_init", "fss_accum", "fss_merge", "fss_compute", "fss_table", "FssAccumulator", "MAX_SCALE", "MAX_SIDE"]
 
@@ -37,21 +37,6 @@ MAX_SCALE = 255  # csrc/fss.hip kFssMaxScale
 MAX_SIDE = 65535  # csrc/fss.hip kFssMaxDim
 _NATIVE = (np.dtype(np.float32), np.dtype(np.float64))
 _SHAPE_MESSAGE = "X_f and X_o must be two-dimensional arrays having the same shape"
-_reference_fss_accum = None  # the reference's fss_accum while register.patch_fss() has replaced it
-
-
-def _reference_accum():
-    if _reference_fss_accum is not None:
-        return _reference_fss_accum
-    try:
-        from pysteps.verification import spatialscores as ref  # noqa: PLC0415
-    except Exception:
-        return None
-    return None if ref.fss_accum is fss_accum else ref.fss_accum
-
-
-def _dtype_of(X):
-    return X.dtype if isinstance(X, DeviceArray) else np.asanyarray(X).dtype
 
 
 def _window(scale):
@@ -84,12 +69,6 @@ def _unsupported(dtypes, shape, thrs, scales):
             if not separated:
                 return "threshold %r (not above threshold - 1 as %s)" % (thr, dtype)
     return None
-
-
-def _upload(X):
-    if isinstance(X, DeviceArray):
-        return X
-    return DeviceArray.from_host(np.ascontiguousarray(np.asarray(X)), sync=False)
 
 
 def _sums(dev_f, dev_o, K, m, n, shared, thr_f, thr_o, scales):
@@ -138,12 +117,9 @@ def fss_accum(fss, X_f, X_o):
     dt_f, dt_o = _dtype_of(X_f), _dtype_of(X_o)
     why = _unsupported((dt_f, dt_o), tuple(X_f.shape), [thr], [scale])
     if why is not None:
-        ref = _reference_accum()
-        if ref is None or isinstance(X_f, DeviceArray) or isinstance(X_o, DeviceArray):
-            raise NotImplementedError("pysteps_amd fss_accum: %s is not implemented on the device%s"
-                                      % (why, "" if ref is not None else " and pysteps is not importable"))
-        warnings.warn("pysteps_amd fss_accum: %s - running the reference's function" % why, stacklevel=2)
-        return ref(fss, X_f, X_o)
+        resident = isinstance(X_f, DeviceArray) or isinstance(X_o, DeviceArray)
+        return decline("fss_accum", why, lookup("verification.spatialscores", "fss_accum", fss_accum), resident,
+                       UserWarning)(fss, X_f, X_o)
     m, n = X_f.shape
     counts = _sums(_upload(X_f), _upload(X_o), 1, m, n, True, [_compared_as(thr, dt_f)], [_compared_as(thr, dt_o)],
                    [scale])[0, 0, 0]

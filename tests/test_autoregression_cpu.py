@@ -43,7 +43,7 @@ def test_patch_and_unpatch(ref_pysteps):
         assert register.patch_autoregression() == ["autoregression:iterate_ar_model"]
         assert ref_mod.iterate_ar_model is hip_mod.iterate_ar_model
         assert register.patch_autoregression() == []
-        assert hip_mod._reference() is stock
+        assert hip_mod._stock() is stock
     finally:
         register.unpatch_autoregression()
     assert ref_mod.iterate_ar_model is stock and not hasattr(ref_mod, "_reference_iterate_ar_model")

@@ -185,7 +185,7 @@ def test_unsupported_shape_delegates(no_device, ref_pysteps):
 def test_unsupported_without_pysteps_raises(no_device, monkeypatch):
     from pysteps_amd.motion import darts
 
-    monkeypatch.setattr(darts, "_reference_darts", lambda: None)
+    monkeypatch.setattr(darts, "lookup", lambda module, name, ours: None)
     with pytest.raises(NotImplementedError, match="device FFT"):
         darts.DARTS(np.zeros((6, 4100, 54)), verbose=False)
 

@@ -504,7 +504,11 @@ def test_registration_is_opt_in(ref_pysteps):
     from pysteps.verification import detcontscores as ref_cont
 
     from pysteps_amd import register
+    from pysteps_amd._reference import lookup
     from pysteps_amd.verification import detcatscores, detcontscores
+
+    def stock(mod, name):
+        return lookup("verification." + mod.__name__.rsplit(".", 1)[1], name, getattr(mod, name))
 
     before = (ref_cat.det_cat_fct, ref_cat.det_cat_fct_accum, ref_cont.det_cont_fct, ref_cont.det_cont_fct_accum)
 
@@ -519,12 +523,12 @@ def test_registration_is_opt_in(ref_pysteps):
         assert current() == (detcatscores.det_cat_fct, detcatscores.det_cat_fct_accum, detcontscores.det_cont_fct,
                              detcontscores.det_cont_fct_accum)
         assert (ref_cat._reference_det_cat_fct, ref_cat._reference_det_cat_fct_accum) == before[:2]
-        assert detcatscores._reference("det_cat_fct_accum") is before[1] and detcontscores._reference("det_cont_fct") is before[2]
+        assert stock(detcatscores, "det_cat_fct_accum") is before[1] and stock(detcontscores, "det_cont_fct") is before[2]
         assert register.patch_detscores() == []  # already in place
         register.unpatch_detscores()
         assert current() == before and not hasattr(ref_cat, "_reference_det_cat_fct")
-        assert detcontscores._reference_fct is None and detcatscores._reference_fct_accum is None
-        assert detcatscores._reference("det_cat_fct") is before[0]
+        assert not [a for mod in (ref_cat, ref_cont) for a in vars(mod) if a.startswith("_reference_")]
+        assert stock(detcatscores, "det_cat_fct") is before[0] and stock(detcontscores, "det_cont_fct_accum") is before[3]
         register.unpatch_detscores()  # harmless when nothing is patched
         assert current() == before
     finally:

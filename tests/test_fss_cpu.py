@@ -280,6 +280,7 @@ def test_registration_is_opt_in(ref_pysteps):
     from pysteps.verification import spatialscores as ref
 
     from pysteps_amd import register
+    from pysteps_amd._reference import lookup
     from pysteps_amd.verification import spatialscores
 
     before = (ref.fss, ref.fss_accum)
@@ -290,11 +291,12 @@ def test_registration_is_opt_in(ref_pysteps):
         assert register.register(fss=True)[-2:] == ["verification:fss", "verification:fss_accum"]
         assert ref.fss is spatialscores.fss and ref.fss_accum is spatialscores.fss_accum
         assert ref_verification.get_method("fss") is spatialscores.fss
-        assert spatialscores._reference_accum() is before[1]
+        assert lookup("verification.spatialscores", "fss_accum", spatialscores.fss_accum) is before[1]
         assert register.patch_fss() == []  # already in place
         register.unpatch_fss()
         assert (ref.fss, ref.fss_accum) == before and ref_verification.get_method("fss") is before[0]
-        assert not hasattr(ref, "_reference_fss") and spatialscores._reference_fss_accum is None
+        assert not hasattr(ref, "_reference_fss") and not hasattr(ref, "_reference_fss_accum")
+        assert lookup("verification.spatialscores", "fss_accum", spatialscores.fss_accum) is before[1]
         register.unpatch_fss()  # harmless when nothing is patched
         assert (ref.fss, ref.fss_accum) == before
     finally:

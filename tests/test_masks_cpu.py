@@ -56,6 +56,7 @@ def test_patch_and_unpatch(ref_pysteps):
     import pysteps.nowcasts.utils as ref_mod
 
     from pysteps_amd import register
+    from pysteps_amd._reference import lookup
     from pysteps_amd.nowcasts import utils as hip_mod
 
     stock = ref_mod.compute_dilated_mask
@@ -63,7 +64,7 @@ def test_patch_and_unpatch(ref_pysteps):
         assert register.patch_dilated_mask() == ["nowcasts.utils:compute_dilated_mask"]
         assert ref_mod.compute_dilated_mask is hip_mod.compute_dilated_mask
         assert register.patch_dilated_mask() == []
-        assert hip_mod._reference_compute_dilated_mask() is stock
+        assert lookup("nowcasts.utils", "compute_dilated_mask", hip_mod.compute_dilated_mask) is stock
     finally:
         register.unpatch_dilated_mask()
     assert ref_mod.compute_dilated_mask is stock and not hasattr(ref_mod, "_reference_compute_dilated_mask")

@@ -77,7 +77,7 @@ def _spied(monkeypatch):
         calls.append((R, args, kwargs))
         return "from the reference"
 
-    monkeypatch.setattr(hip_mod, "_reference_fn", spy)
+    monkeypatch.setattr(hip_mod, "lookup", lambda module, name, ours: spy)
     return hip_mod, calls
 
 
@@ -125,7 +125,7 @@ def test_without_pysteps_a_declined_call_raises(small_case, monkeypatch):
     from pysteps_amd.noise import utils as hip_mod
 
     R, F, noise_filter = small_case
-    monkeypatch.setattr(hip_mod, "_reference", lambda: None)
+    monkeypatch.setattr(hip_mod, "lookup", lambda module, name, ours: None)
     with pytest.raises(NotImplementedError, match="decomp_method"):
         hip_mod.compute_noise_stddev_adjs(R, -10.0, -15.0, F, hip_mod._is_fn, noise_filter, hip_mod._is_fn, 0)
 
@@ -144,11 +144,12 @@ def test_patch_and_unpatch_swap_the_attribute(ref_pysteps):
     try:
         assert register.patch_noise_stddev_adj() == ["noise.utils:compute_noise_stddev_adjs"]
         assert ref_mod.compute_noise_stddev_adjs is hip_mod.compute_noise_stddev_adjs
-        assert hip_mod._reference() is stock
+        assert hip_mod.lookup("noise.utils", "compute_noise_stddev_adjs", hip_mod.compute_noise_stddev_adjs) is stock
         assert register.patch_noise_stddev_adj() == []
     finally:
         register.unpatch_noise_stddev_adj()
-    assert ref_mod.compute_noise_stddev_adjs is stock and hip_mod._reference_fn is None
+    assert ref_mod.compute_noise_stddev_adjs is stock
+    assert hip_mod.lookup("noise.utils", "compute_noise_stddev_adjs", hip_mod.compute_noise_stddev_adjs) is stock
     assert not hasattr(ref_mod, "_reference_compute_noise_stddev_adjs")
     try:
         added = register.register(noise_stddev_adj=True)

@@ -367,7 +367,7 @@ def test_declined_inputs_go_to_the_reference_with_a_warning(golden, host_kernel,
         ps.crps_table(many[:3], obs[:2])
     with pytest.raises(ValueError):
         ps.reldiag_accum(ps.reldiag_init(x_min), p, o[:5])
-    monkeypatch.setattr(ps, "_reference", lambda name: None)  # pysteps is not importable: nothing to hand the input to
+    monkeypatch.setattr(ps, "lookup", lambda module, name, ours: None)  # pysteps is not importable: nothing to hand the input to
     with pytest.raises(NotImplementedError, match="65 members .* pysteps is not importable"):
         ps.CRPS(many, obs)
     with pytest.raises(NotImplementedError, match="dtype float16"):
@@ -384,7 +384,11 @@ def test_registration_is_opt_in(ref_pysteps):
     from pysteps.verification import probscores as ref
 
     from pysteps_amd import register
+    from pysteps_amd._reference import lookup
     from pysteps_amd.verification import probscores
+
+    def stock(name):
+        return lookup("verification.probscores", name, getattr(probscores, name))
 
     def current():
         return tuple(getattr(ref, name) for name in probscores.SWAPPED)
@@ -397,15 +401,15 @@ def test_registration_is_opt_in(ref_pysteps):
         assert register.register(probscores=True)[-6:] == ["verification:" + name for name in probscores.SWAPPED]
         assert current() == tuple(getattr(probscores, name) for name in probscores.SWAPPED)
         assert kept == (ref.CRPS_init, ref.CRPS_compute, ref.reldiag_init, ref.reldiag_compute, ref.ROC_curve_init, ref.ROC_curve_compute)
-        assert ref._reference_CRPS_accum is before[1] and probscores._reference("CRPS_accum") is before[1]
-        assert probscores._reference("ROC_curve") is before[4]
+        assert ref._reference_CRPS_accum is before[1] and stock("CRPS_accum") is before[1]
+        assert stock("ROC_curve") is before[4]
         import pysteps.verification
 
         assert pysteps.verification.get_method("crps", type="probabilistic") is probscores.CRPS
         assert register.patch_probscores() == []  # already in place
         register.unpatch_probscores()
-        assert current() == before and not hasattr(ref, "_reference_CRPS") and not probscores._held
-        assert probscores._reference("reldiag_accum") is before[3]
+        assert current() == before and not [a for a in vars(ref) if a.startswith("_reference_")]
+        assert stock("reldiag_accum") is before[3]
         register.unpatch_probscores()  # harmless when nothing is patched
         assert current() == before
     finally:

@@ -147,6 +147,7 @@ def test_register_swaps_and_restores_the_attribute(ref_pysteps):
     from pysteps import utils as ref_utils
 
     from pysteps_amd import register
+    from pysteps_amd._reference import lookup
     from pysteps_amd.utils import spectral
 
     original = ref_mod.rapsd
@@ -157,12 +158,12 @@ def test_register_swaps_and_restores_the_attribute(ref_pysteps):
         added = register.register(fft=False, rapsd=True)
         assert "utils.spectral:rapsd" in added and ref_mod.rapsd is spectral.rapsd
         assert ref_utils.interface.get_method("rapsd") is spectral.rapsd
-        assert spectral._reference() is original
+        assert lookup("utils.spectral", "rapsd", spectral.rapsd) is original
         assert register.patch_rapsd() == []  # twice is once
     finally:
         register.unpatch_rapsd()
-    assert ref_mod.rapsd is original and spectral._reference_rapsd is None and not hasattr(ref_mod, "_reference_rapsd")
-    assert spectral._reference() is original
+    assert ref_mod.rapsd is original and not hasattr(ref_mod, "_reference_rapsd")
+    assert lookup("utils.spectral", "rapsd", spectral.rapsd) is original
 
 
 def test_declined_shape_and_dtype_run_the_reference_for_every_method(ref_pysteps):
