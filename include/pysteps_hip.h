@@ -484,6 +484,38 @@ int psh_darts_rows_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int
 int psh_darts_synth_dev(const int *ky_host, const int *kx_host, const void *values_host, int nb, int m, int n, int f32,
                         void *out_dev);
 
+/* ---- the Proesmans motion estimate (csrc/proesmans.hip) --------------------------------------------------------- *
+ * pysteps/motion/proesmans.py and _proesmans.pyx in float64 with the reference's operations in the reference's order
+ * (no fused multiply-adds): given the same K every plane equals the reference's bit for bit.  V is (2, 2, m, n):
+ * [forward / backward][x, y]; GAMMA (2, m, n).  Every call is queued on the library stream.
+ *  psh_proesmans_scale_dev   `count` values (float32 if f32, widened exactly, else float64) -> out float64:
+ *      (v - min) / (max - min) * 255.0 when max - min > 1e-8, else v; range_host = {min, max, number of non-finite
+ *      values} (min and max over the finite ones) from a deterministic two-stage reduction; waits for the result.
+ *  psh_proesmans_pyramid_dev  src (m, n) -> dst (m / 2, n / 2): (a + b + c + d) / 4.0, an odd last row / column dropped.
+ *  psh_proesmans_gradients_dev  frame (m, n) -> grad (2, m, n): the two scipy.ndimage.convolve(mode="constant") of
+ *      _compute_gradients, taps summed in SciPy's order.
+ *  psh_proesmans_consistency_dev  _compute_consistency_maps: V -> gamma.  raw (2, m, n) (may be NULL) receives the c
+ *      planes before normalisation (-1 outside the image), stats (may be NULL) 8 doubles: per direction {c_sum, c_count,
+ *      K, 0}.  c_sum is a double-double sum in a fixed order, rounded once; K stays on the device.
+ *  psh_proesmans_sweep_dev   one iteration's update of both directions of V in place, in the reference's dependency
+ *      order (a Gauss-Seidel sweep, evaluated along t = x + 2 y), then _fill_edges.  frames (2, m, n) of this level,
+ *      grad (2, 2, m, n) = [frame][gx, gy].  No kernel waits for another workgroup.
+ *  psh_proesmans_sweep_launches  the kernel launches psh_proesmans_sweep_dev makes for this shape (pure function).
+ *  psh_proesmans_next_level_dev  _initialize_next_level: V_prev (2, 2, m_prev, n_prev) -> V_next (2, 2, m_next, n_next).
+ *  psh_proesmans_dev         _compute_advection_field on scaled frames (2, m, n): V (2, 2, m, n) and gamma (2, m, n),
+ *      float32 (f32, rounded once at the final store) or float64.  PSH_EUNSUPPORTED when the coarsest level has a side
+ *      below 3. */
+int psh_proesmans_scale_dev(const void *frames_dev, int f32, size_t count, double *out_dev, double *range_host);
+int psh_proesmans_pyramid_dev(const double *src_dev, int m, int n, double *dst_dev);
+int psh_proesmans_gradients_dev(const double *frame_dev, int m, int n, double *grad_dev);
+int psh_proesmans_consistency_dev(const double *V_dev, int m, int n, double *gamma_dev, double *raw_dev, double *stats_dev);
+int psh_proesmans_sweep_dev(const double *frames_dev, const double *grad_dev, const double *gamma_dev, double *V_dev, int m,
+                            int n, double lam);
+int psh_proesmans_sweep_launches(int m, int n);
+int psh_proesmans_next_level_dev(const double *V_prev_dev, int m_prev, int n_prev, double *V_next_dev, int m_next, int n_next);
+int psh_proesmans_dev(const double *frames_dev, int m, int n, double lam, int num_iter, int num_levels, int f32, void *V_dev,
+                      void *gamma_dev);
+
 /* ---- RainFARM stochastic downscaling (csrc/rainfarm.hip) ------------------------------------------------------ *
  * pysteps/downscaling/rainfarm.py ``downscale`` without spectral fusion for K realisations; (m, n) is the
  * low-resolution shape, ds the factor, (M, N) = (m ds, n ds); float64; every call is queued on the library stream.

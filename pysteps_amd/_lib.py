@@ -126,6 +126,14 @@ SIGNATURES = {
     "psh_darts_gram_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p]),
     "psh_darts_rows_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     "psh_darts_synth_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "psh_proesmans_scale_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, POINTER(c_double)]),
+    "psh_proesmans_pyramid_dev": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "psh_proesmans_gradients_dev": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "psh_proesmans_consistency_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "psh_proesmans_sweep_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_double]),
+    "psh_proesmans_sweep_launches": (c_int, [c_int, c_int]),
+    "psh_proesmans_next_level_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int]),
+    "psh_proesmans_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_int, c_int, c_int, c_void_p, c_void_p]),
     "psh_rainfarm_spectrum_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p]),
     "psh_rainfarm_std_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     "psh_rainfarm_exp_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

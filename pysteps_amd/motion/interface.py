@@ -1,7 +1,7 @@
 """``motion.get_method`` mirror (reference: pysteps/motion/interface.py:36-111).
 
-"lk"/"lucaskanade" resolve to the HIP dense Lucas-Kanade, "darts_hip" to the HIP DARTS; ``None`` returns the
-reference's zero-motion callable; the other reference methods (vet, darts,
+"lk"/"lucaskanade" resolve to the HIP dense Lucas-Kanade, "darts_hip" to the HIP DARTS, "proesmans_hip" to the HIP
+Proesmans estimate; ``None`` returns the reference's zero-motion callable; the other reference methods (vet, darts,
 proesmans, constant, farneback) are different algorithms outside this package and
 are forwarded to pysteps when it is importable.
 """
@@ -11,6 +11,7 @@ import numpy as np
 from .._registry import MethodTable
 from .darts import DARTS
 from .lucaskanade import dense_lucaskanade
+from .proesmans import proesmans
 
 _OTHER_REFERENCE_METHODS = ("vet", "darts", "proesmans", "constant", "farneback")
 
@@ -23,6 +24,7 @@ def _zero_motion(precip, *args, **kwargs):
 _table = MethodTable("optical flow")
 _table.add(["lk", "lucaskanade", "lk_hip", "lucaskanade_hip"], dense_lucaskanade)
 _table.add("darts_hip", DARTS)
+_table.add("proesmans_hip", proesmans)
 _table.add(None, _zero_motion)
 
 

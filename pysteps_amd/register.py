@@ -21,6 +21,7 @@ BPS_NAME = "bps_hip"  # vel_pert_method: the reference's generate_bps behind an 
 EXTRAPOLATION_NAMES = ("semilagrangian_hip",)
 MOTION_NAMES = ("lk_hip", "lucaskanade_hip")
 DARTS_NAME = "darts_hip"  # the stock "darts" stays the reference's, with or without override
+PROESMANS_NAME = "proesmans_hip"  # likewise the stock "proesmans"
 FEATURE_NAMES = {"blob_hip": "blob", "shitomasi_hip": "shitomasi"}  # pysteps.feature.get_method(...)
 POSTPROCESSING_NAMES = {"mean": "mean", "excprob": "excprob"}  # pysteps.postprocessing.get_method(name + "_hip", "ensemblestats")
 _STOCK_EXTRAPOLATION = ("semilagrangian",)
@@ -32,6 +33,7 @@ def register_into(motion_methods, extrapolation_methods, override=False):
     from .extrapolation.semilagrangian import extrapolate
     from .motion.darts import DARTS
     from .motion.lucaskanade import dense_lucaskanade
+    from .motion.proesmans import proesmans
 
     added = []
     if extrapolation_methods is not None:
@@ -44,6 +46,8 @@ def register_into(motion_methods, extrapolation_methods, override=False):
             added.append("motion:" + name)
         motion_methods[DARTS_NAME] = DARTS
         added.append("motion:" + DARTS_NAME)
+        motion_methods[PROESMANS_NAME] = proesmans
+        added.append("motion:" + PROESMANS_NAME)
     return added
 
 
