@@ -540,6 +540,35 @@ int psh_rainfarm_finish_dev(const double *e_dev, const double *precip_dev, int p
                             int m, int n, int ds, const double *table_dev, int na, int amin, int has_threshold,
                             double threshold, int f32, void *out_dev);
 
+/* ---- linear and salient blending with NWP (csrc/blending.hip) ------------------------------------------------- *
+ * pysteps/blending/linear_blending.py, one lead time of K member pairs per call, queued on the library stream.
+ * offsets (3, K) int64 on the device: element offsets of member pair k's nowcast plane (from nowcast_dev), NWP plane
+ * (from nwp_dev) and result plane (from out_dev); *_f32 != 0: float32, else float64; the result has the NWP's dtype.
+ * The NWP is read through np.nan_to_num(nan=0.0); nowcast NaNs take that value cast to the nowcast's dtype (0 with
+ * fill_nwp == 0).
+ *  psh_blend_linear_dev  mode 0: the filled nowcast (the NWP may be NULL with fill_nwp == 0); 1: the NWP (the nowcast
+ *      is not read); 2: weight_nwp * nwp + weight_nowcast * nowcast, each product in its array's dtype with the weight
+ *      rounded to it, the sum in the common dtype, no fused multiply-add.
+ *  psh_blend_salient_dev  Hwang et al. (2015): both maxima and the dense ranks of nowcast / max - nwp / max over all
+ *      K planes jointly, ws = _get_ws(weight, rank / distinct) in float64, ws * nowcast + (1 - ws) * nwp.  The squares
+ *      come from the host (Python's weight ** 2).  Synchronous.  *status != 0: declined, nothing was written (1: a
+ *      maximum is not finite, 2: a difference is NaN).  stage_ms (NULL or 5 floats): device time of {maxima, keys and
+ *      histograms; sort passes; distinct keys; rank lookup and blend; all}.  At most 2^31 values (PSH_EUNSUPPORTED).
+ *  psh_blend_dense_rank_dev  rank (n) uint32 = scipy.stats.rankdata(x, "dense") of n finite values, -0.0 ranked with
+ *      0.0; *distinct (host) = the largest rank.  Synchronous.
+ *  psh_blend_db_inverse_f64_dev  the inverse dB transform in float64: r < threshold_db ? zerovalue : 10^(r/10).
+ *  psh_blend_scale_dev  out = in / divisor * factor in the array's dtype (accumulation in mm -> mm/h). */
+int psh_blend_linear_dev(const void *nowcast_dev, int nowcast_f32, const void *nwp_dev, int nwp_f32,
+                         const long long *offsets_dev, int K, size_t plane, int mode, double weight_nwp,
+                         double weight_nowcast, int fill_nwp, void *out_dev);
+int psh_blend_salient_dev(const void *nowcast_dev, int nowcast_f32, const void *nwp_dev, int nwp_f32,
+                          const long long *offsets_dev, int K, size_t plane, double weight, double one_minus_weight,
+                          double weight_sq, double one_minus_weight_sq, int fill_nwp, void *out_dev, int *status,
+                          float *stage_ms);
+int psh_blend_dense_rank_dev(const void *x_dev, int f32, size_t n, unsigned *rank_dev, unsigned *distinct);
+int psh_blend_db_inverse_f64_dev(const double *in_dev, double *out_dev, size_t n, double threshold_db, double zerovalue);
+int psh_blend_scale_dev(const void *in_dev, void *out_dev, int f32, size_t n, double divisor, double factor);
+
 /* ---- dense Lucas-Kanade: image front end ----------------------------------- *
  * The NumPy + OpenCV stages of pysteps/motion/lucaskanade.py:205-242, per frame /
  * frame pair.  OpenCV is a third-party dependency of the reference (not in its

@@ -139,6 +139,13 @@ SIGNATURES = {
     "psh_rainfarm_exp_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "psh_rainfarm_finish_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
                                         c_int, c_int, c_double, c_int, c_void_p]),
+    "psh_blend_linear_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_size_t, c_int, c_double, c_double, c_int,
+                                     c_void_p]),
+    "psh_blend_salient_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_size_t, c_double, c_double, c_double,
+                                      c_double, c_int, c_void_p, POINTER(c_int), POINTER(c_float)]),
+    "psh_blend_dense_rank_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, POINTER(ctypes.c_uint)]),
+    "psh_blend_db_inverse_f64_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_double, c_double]),
+    "psh_blend_scale_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_double, c_double]),
     "psh_steps_mask_probmatch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psh_dilated_mask_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "psh_steps_incremental_mask_dev": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -32,6 +32,12 @@ def require(module, name, ours):
     return fn
 
 
+def method(package, name):
+    """``pysteps.<package>.get_method(name)``: a method this package does not serve, from the reference's own table
+    (the import's own error when pysteps is absent)."""
+    return importlib.import_module("pysteps." + package).get_method(name)
+
+
 def _is_fn(obj, module_suffix, name):
     """``obj`` is the function ``name`` of a module ending in ``module_suffix`` (the reference's or ours)."""
     return callable(obj) and getattr(obj, "__name__", "") == name and getattr(obj, "__module__", "").endswith(module_suffix)

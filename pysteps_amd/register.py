@@ -24,7 +24,8 @@ DARTS_NAME = "darts_hip"  # the stock "darts" stays the reference's, with or wit
 PROESMANS_NAME = "proesmans_hip"  # likewise the stock "proesmans"
 FEATURE_NAMES = {"blob_hip": "blob", "shitomasi_hip": "shitomasi"}  # pysteps.feature.get_method(...)
 POSTPROCESSING_NAMES = {"mean": "mean", "excprob": "excprob"}  # pysteps.postprocessing.get_method(name + "_hip", "ensemblestats")
-_STOCK_EXTRAPOLATION = ("semilagrangian",)
+BLENDING_NAMES = ("linear_blending_hip", "salient_blending_hip")  # the stock names stay the reference's
+_STOCK_EXTRAPOLATION =("semilagrangian",)
 _STOCK_MOTION = ("lk", "lucaskanade")
 
 
@@ -286,6 +287,21 @@ def register_downscaling():
     return ["downscaling:rainfarm_hip"]
 
 
+def register_blending():
+    """Add ``"linear_blending_hip"`` and ``"salient_blending_hip"`` (:func:`pysteps_amd.blending.linear_blending.forecast`,
+    the latter with ``saliency=True``) to pysteps' blending table (pysteps/blending/interface.py
+    ``_blending_methods``); the stock ``"linear_blending"`` and ``"salient_blending"`` stay the reference's."""
+    import pysteps.blending.interface as blend_if  # noqa: PLC0415
+
+    from .blending.interface import get_method  # noqa: PLC0415
+
+    added = []
+    for name in BLENDING_NAMES:
+        blend_if._blending_methods[name] = get_method(name)
+        added.append("blending:" + name)
+    return added
+
+
 def register_postprocessing(override=False):
     """Add ``"mean_hip"`` and ``"excprob_hip"`` (:mod:`pysteps_amd.postprocessing.ensemblestats`) to pysteps' ensemble
     statistics table (pysteps/postprocessing/interface.py ``_ensemblestats_methods``:
@@ -328,7 +344,8 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     ``pysteps.verification.probscores`` accumulate the CRPS, reliability diagrams and ROC curves on the device
     (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it).
 
-    ``"rainfarm_hip"`` joins ``pysteps.downscaling``'s method table (:func:`register_downscaling`)."""
+    ``"rainfarm_hip"`` joins ``pysteps.downscaling``'s method table (:func:`register_downscaling`), and
+    ``"linear_blending_hip"`` and ``"salient_blending_hip"`` join ``pysteps.blending``'s (:func:`register_blending`)."""
     import pysteps.extrapolation.interface as ext_if  # noqa: PLC0415
     import pysteps.motion.interface as mot_if  # noqa: PLC0415
 
@@ -349,6 +366,10 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += register_downscaling()
     except ImportError:
         pass  # an older or stripped-down install may lack pysteps.downscaling
+    try:
+        added += register_blending()
+    except ImportError:
+        pass  # pysteps.blending imports every blending module; a stripped-down install may lack one's dependencies
     if fft:
         added += register_fft()
         added += register_spectral()
