@@ -307,32 +307,27 @@ int gauss(const double *in0, const double *in1, const double *in2, int recipe, i
   }
   const size_t plane = static_cast<size_t>(m) * n;
   const size_t wbytes = (static_cast<size_t>(r + 1) * sizeof(double) + 255) & ~static_cast<size_t>(255);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, wbytes + static_cast<size_t>(nf) * plane * sizeof(double))) return rc;
-  double *w = static_cast<double *>(blk);
-  double *tmp = reinterpret_cast<double *>(static_cast<char *>(blk) + wbytes);
-  auto run = [&]() -> int {
-    // (the caller's weights may go once this call returns: the copy is waited for)
-    PSH_HIP(hipMemcpyAsync(w, weights_host, static_cast<size_t>(r + 1) * sizeof(double), hipMemcpyHostToDevice, s));
-    PSH_HIP(hipStreamSynchronize(s));
-    switch (recipe * 4 + nin) {
-      case kPlain * 4 + 1: launch_axis0<kPlain, 1, 1>(in0, in1, in2, m, n, w, r, tmp, s); break;
-      case kPlain * 4 + 2: launch_axis0<kPlain, 2, 2>(in0, in1, in2, m, n, w, r, tmp, s); break;
-      case kPlain * 4 + 3: launch_axis0<kPlain, 3, 3>(in0, in1, in2, m, n, w, r, tmp, s); break;
-      case kCorr * 4 + 2: launch_axis0<kCorr, 2, 3>(in0, in1, in2, m, n, w, r, tmp, s); break;
-      case kCorr * 4 + 3: launch_axis0<kCorr, 3, 5>(in0, in1, in2, m, n, w, r, tmp, s); break;
-      case kRvil * 4 + 3: launch_axis0<kRvil, 3, 5>(in0, in1, in2, m, n, w, r, tmp, s); break;
-      default: launch_axis0<kOnes, 0, 1>(in0, in1, in2, m, n, w, r, tmp, s); break;
-    }
-    const size_t lds = static_cast<size_t>(kAnvilThreads + 2 * r) * sizeof(double);
-    hipLaunchKernelGGL(anvil_gauss_axis1, dim3((n + kAnvilThreads - 1) / kAnvilThreads, m), dim3(kAnvilThreads), lds, s,
-                       static_cast<const double *>(tmp), nf, m, n, static_cast<const double *>(w), r, out);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(wbytes + static_cast<size_t>(nf) * plane * sizeof(double))) return rc;
+  double *w = blk.as<double>();
+  double *tmp = blk.at<double>(wbytes);
+  // (the caller's weights may go once this call returns: the copy is waited for)
+  PSH_HIP(hipMemcpyAsync(w, weights_host, static_cast<size_t>(r + 1) * sizeof(double), hipMemcpyHostToDevice, s));
+  PSH_HIP(hipStreamSynchronize(s));
+  switch (recipe * 4 + nin) {
+    case kPlain * 4 + 1: launch_axis0<kPlain, 1, 1>(in0, in1, in2, m, n, w, r, tmp, s); break;
+    case kPlain * 4 + 2: launch_axis0<kPlain, 2, 2>(in0, in1, in2, m, n, w, r, tmp, s); break;
+    case kPlain * 4 + 3: launch_axis0<kPlain, 3, 3>(in0, in1, in2, m, n, w, r, tmp, s); break;
+    case kCorr * 4 + 2: launch_axis0<kCorr, 2, 3>(in0, in1, in2, m, n, w, r, tmp, s); break;
+    case kCorr * 4 + 3: launch_axis0<kCorr, 3, 5>(in0, in1, in2, m, n, w, r, tmp, s); break;
+    case kRvil * 4 + 3: launch_axis0<kRvil, 3, 5>(in0, in1, in2, m, n, w, r, tmp, s); break;
+    default: launch_axis0<kOnes, 0, 1>(in0, in1, in2, m, n, w, r, tmp, s); break;
+  }
+  const size_t lds = static_cast<size_t>(kAnvilThreads + 2 * r) * sizeof(double);
+  hipLaunchKernelGGL(anvil_gauss_axis1, dim3((n + kAnvilThreads - 1) / kAnvilThreads, m), dim3(kAnvilThreads), lds, s,
+                     static_cast<const double *>(tmp), nf, m, n, static_cast<const double *>(w), r, out);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 int check_shape(const char *what, int m, int n) {
@@ -390,21 +385,16 @@ extern "C" int psh_anvil_rvil_dev(const double *vil_dev, const double *rainrate_
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const size_t count = static_cast<size_t>(m) * n;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 8 * count * sizeof(double))) return rc;
-  double *planes = static_cast<double *>(blk), *sums = planes + 3 * count;
-  auto run = [&]() -> int {
-    hipLaunchKernelGGL(anvil_rvil_prep, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, vil_dev, rainrate_dev, count, planes);
-    PSH_HIP(hipGetLastError());
-    if (int rc = gauss(planes, planes + count, planes + 2 * count, kRvil, m, n, weights_host, radius, sums, c.stream)) return rc;
-    hipLaunchKernelGGL(anvil_rvil_solve, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, vil_dev,
-                       static_cast<const double *>(sums), count, a_dev, b_dev);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(8 * count * sizeof(double))) return rc;
+  double *planes = blk.as<double>(), *sums = planes + 3 * count;
+  hipLaunchKernelGGL(anvil_rvil_prep, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, vil_dev, rainrate_dev, count, planes);
+  PSH_HIP(hipGetLastError());
+  if (int rc = gauss(planes, planes + count, planes + 2 * count, kRvil, m, n, weights_host, radius, sums, c.stream)) return rc;
+  hipLaunchKernelGGL(anvil_rvil_solve, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, vil_dev,
+                     static_cast<const double *>(sums), count, a_dev, b_dev);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 extern "C" int psh_anvil_masks_dev(const double *frames_dev, int K, int m, int n, double *zeroed_dev, unsigned char *mask_dev,

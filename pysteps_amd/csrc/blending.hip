@@ -679,8 +679,7 @@ extern "C" int psh_blend_dense_rank_dev(const void *x_dev, int f32, size_t n, un
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  if (f32) return psh::rank_impl(static_cast<const float *>(x_dev), n, rank_dev, distinct, c.stream);
-  return psh::rank_impl(static_cast<const double *>(x_dev), n, rank_dev, distinct, c.stream);
+  return psh::with_real(x_dev, !f32, [&](auto *x) { return psh::rank_impl(x, n, rank_dev, distinct, c.stream); });
 }
 
 extern "C" int psh_blend_db_inverse_f64_dev(const double *in_dev, double *out_dev, size_t n, double threshold_db, double zerovalue) {

@@ -218,52 +218,47 @@ int blob_cube(const T *image, int m, int n, int method, const double *sigmas, in
   // [weights | tmp_a | tmp_b | g_prev | g_cur]
   const size_t wbytes = (wtotal * sizeof(double) + 255) & ~static_cast<size_t>(255);
   const size_t pbytes = (plane * sizeof(T) + 255) & ~static_cast<size_t>(255);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, wbytes + 4 * pbytes)) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(wbytes + 4 * pbytes)) return rc;
+  char *base = blk.as<char>();
   double *w_dev = reinterpret_cast<double *>(base);
   T *tmp_a = reinterpret_cast<T *>(base + wbytes), *tmp_b = reinterpret_cast<T *>(base + wbytes + pbytes);
   T *g_prev = reinterpret_cast<T *>(base + wbytes + 2 * pbytes), *g_cur = reinterpret_cast<T *>(base + wbytes + 3 * pbytes);
-  auto run = [&]() -> int {
-    // (the caller's array may go once this call returns: the copy is waited for - a detection is not a launch chain
-    // anybody queues behind)
-    PSH_HIP(hipMemcpyAsync(w_dev, weights, wtotal * sizeof(double), hipMemcpyHostToDevice, stream));
-    PSH_HIP(hipStreamSynchronize(stream));
-    const dim3 grid0((n + 63) / 64, (m + 3) / 4), grid1((n + kBlobThreads - 1) / kBlobThreads, m);
-    const size_t lds = 2 * static_cast<size_t>(kBlobThreads + 2 * rmax) * sizeof(double);
-    if (lds > 64 * 1024) PSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&blob_corr_axis1<T>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    size_t woff = 0;
-    for (int k = 0; k < nsig; ++k) {
-      const int r = radius[k];
-      const double *w_g = w_dev + woff, *w_d2 = w_g + (r + 1);
-      woff += 2 * static_cast<size_t>(r + 1);
-      const size_t lds_k = 2 * static_cast<size_t>(kBlobThreads + 2 * r) * sizeof(double);
-      if (method == 0) {
-        // rows: tmp_a = G'' image, tmp_b = G image; columns: G tmp_a + G'' tmp_b -> cube[k]
-        hipLaunchKernelGGL(blob_corr_axis0<T>, grid0, dim3(kBlobThreads), 0, stream, image, m, n, w_d2, w_g, r, tmp_a, tmp_b);
-        hipLaunchKernelGGL(blob_corr_axis1<T>, grid1, dim3(kBlobThreads), lds_k, stream, static_cast<const T *>(tmp_a),
-                           static_cast<const T *>(tmp_b), m, n, w_g, w_d2, r, sigmas[k] * sigmas[k], static_cast<T *>(nullptr),
-                           cube + static_cast<size_t>(k) * plane);
-      } else {
-        hipLaunchKernelGGL(blob_corr_axis0<T>, grid0, dim3(kBlobThreads), 0, stream, image, m, n, w_g, static_cast<const double *>(nullptr),
-                           r, tmp_a, static_cast<T *>(nullptr));
-        hipLaunchKernelGGL(blob_corr_axis1<T>, grid1, dim3(kBlobThreads), lds_k, stream, static_cast<const T *>(tmp_a),
-                           static_cast<const T *>(nullptr), m, n, w_g, static_cast<const double *>(nullptr), r, 0.0, g_cur,
-                           static_cast<double *>(nullptr));
-        if (k > 0) {
-          const unsigned grid = static_cast<unsigned>(std::min<size_t>((plane + kBlobThreads - 1) / kBlobThreads, 8192));
-          hipLaunchKernelGGL(blob_dog_plane<T>, dim3(grid), dim3(kBlobThreads), 0, stream, static_cast<const T *>(g_prev),
-                             static_cast<const T *>(g_cur), plane, sigmas[k - 1], cube + static_cast<size_t>(k - 1) * plane);
-        }
-        std::swap(g_prev, g_cur);
+  // (the caller's array may go once this call returns: the copy is waited for - a detection is not a launch chain
+  // anybody queues behind)
+  PSH_HIP(hipMemcpyAsync(w_dev, weights, wtotal * sizeof(double), hipMemcpyHostToDevice, stream));
+  PSH_HIP(hipStreamSynchronize(stream));
+  const dim3 grid0((n + 63) / 64, (m + 3) / 4), grid1((n + kBlobThreads - 1) / kBlobThreads, m);
+  const size_t lds = 2 * static_cast<size_t>(kBlobThreads + 2 * rmax) * sizeof(double);
+  if (lds > 64 * 1024) PSH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&blob_corr_axis1<T>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  size_t woff = 0;
+  for (int k = 0; k < nsig; ++k) {
+    const int r = radius[k];
+    const double *w_g = w_dev + woff, *w_d2 = w_g + (r + 1);
+    woff += 2 * static_cast<size_t>(r + 1);
+    const size_t lds_k = 2 * static_cast<size_t>(kBlobThreads + 2 * r) * sizeof(double);
+    if (method == 0) {
+      // rows: tmp_a = G'' image, tmp_b = G image; columns: G tmp_a + G'' tmp_b -> cube[k]
+      hipLaunchKernelGGL(blob_corr_axis0<T>, grid0, dim3(kBlobThreads), 0, stream, image, m, n, w_d2, w_g, r, tmp_a, tmp_b);
+      hipLaunchKernelGGL(blob_corr_axis1<T>, grid1, dim3(kBlobThreads), lds_k, stream, static_cast<const T *>(tmp_a),
+                         static_cast<const T *>(tmp_b), m, n, w_g, w_d2, r, sigmas[k] * sigmas[k], static_cast<T *>(nullptr),
+                         cube + static_cast<size_t>(k) * plane);
+    } else {
+      hipLaunchKernelGGL(blob_corr_axis0<T>, grid0, dim3(kBlobThreads), 0, stream, image, m, n, w_g, static_cast<const double *>(nullptr),
+                         r, tmp_a, static_cast<T *>(nullptr));
+      hipLaunchKernelGGL(blob_corr_axis1<T>, grid1, dim3(kBlobThreads), lds_k, stream, static_cast<const T *>(tmp_a),
+                         static_cast<const T *>(nullptr), m, n, w_g, static_cast<const double *>(nullptr), r, 0.0, g_cur,
+                         static_cast<double *>(nullptr));
+      if (k > 0) {
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>((plane + kBlobThreads - 1) / kBlobThreads, 8192));
+        hipLaunchKernelGGL(blob_dog_plane<T>, dim3(grid), dim3(kBlobThreads), 0, stream, static_cast<const T *>(g_prev),
+                           static_cast<const T *>(g_cur), plane, sigmas[k - 1], cube + static_cast<size_t>(k - 1) * plane);
       }
+      std::swap(g_prev, g_cur);
     }
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  }
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 }  // namespace
@@ -284,9 +279,9 @@ extern "C" int psh_blob_cube_dev(const void *image_dev, int image_is_f32, int m,
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  if (image_is_f32)
-    return psh::blob_cube(static_cast<const float *>(image_dev), m, n, method, sigmas_host, nsig, radius_host, weights_host, cube_dev, c.stream);
-  return psh::blob_cube(static_cast<const double *>(image_dev), m, n, method, sigmas_host, nsig, radius_host, weights_host, cube_dev, c.stream);
+  return psh::with_real(image_dev, !image_is_f32, [&](auto *image) {
+    return psh::blob_cube(image, m, n, method, sigmas_host, nsig, radius_host, weights_host, cube_dev, c.stream);
+  });
 }
 
 extern "C" int psh_blob_peaks_dev(const double *cube_dev, int K, int m, int n, double threshold, int capacity, int *coords_host,
@@ -302,47 +297,42 @@ extern "C" int psh_blob_peaks_dev(const double *cube_dev, int K, int m, int n, d
   const size_t cbytes = (total * sizeof(double) + 255) & ~static_cast<size_t>(255);
   const size_t lbytes = (static_cast<size_t>(capacity) * 3 * sizeof(int) + 255) & ~static_cast<size_t>(255);
   const size_t vbytes = (static_cast<size_t>(capacity) * sizeof(double) + 255) & ~static_cast<size_t>(255);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 256 + cbytes + lbytes + vbytes)) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(256 + cbytes + lbytes + vbytes)) return rc;
+  char *base = blk.as<char>();
   unsigned *counters = reinterpret_cast<unsigned *>(base);
   double *cmax = reinterpret_cast<double *>(base + 256);
   int *coords = reinterpret_cast<int *>(base + 256 + cbytes);
   double *values = reinterpret_cast<double *>(base + 256 + cbytes + lbytes);
   unsigned host_counters[2] = {0u, 0u};
-  auto run = [&]() -> int {
-    hipStream_t s = c.stream;
-    PSH_HIP(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned), s));
-    auto blocks = [](size_t lines) { return dim3(static_cast<unsigned>((lines + kBlobThreads - 1) / kBlobThreads)); };
-    // maximum_filter1d along the image rows' index (axis 0 of scikit-image's (m, n, K) cube), the columns' (axis 1), the scales (axis 2)
-    hipLaunchKernelGGL(blob_max3_lines, blocks(static_cast<size_t>(K) * n), dim3(kBlobThreads), 0, s, cube_dev, cmax,
-                       static_cast<size_t>(K) * n, static_cast<size_t>(n), plane, m, static_cast<size_t>(n));
-    hipLaunchKernelGGL(blob_max3_lines, blocks(static_cast<size_t>(K) * m), dim3(kBlobThreads), 0, s, static_cast<const double *>(cmax), cmax,
-                       static_cast<size_t>(K) * m, static_cast<size_t>(1), static_cast<size_t>(n), n, static_cast<size_t>(1));
-    hipLaunchKernelGGL(blob_max3_lines, blocks(plane), dim3(kBlobThreads), 0, s, static_cast<const double *>(cmax), cmax, plane,
-                       plane, static_cast<size_t>(0), K, plane);
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>((total + kBlobThreads - 1) / kBlobThreads, 8192));
-    hipLaunchKernelGGL(blob_collect, dim3(grid), dim3(kBlobThreads), 0, s, cube_dev, static_cast<const double *>(cmax), K, m, n, threshold,
-                       capacity, coords, values, counters);
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(host_counters, counters, sizeof(host_counters), hipMemcpyDeviceToHost, s));
-    PSH_HIP(hipStreamSynchronize(s));
-    if (host_counters[1] == 0u) {  // peak.py _get_peak_mask: "no peak for a trivial image"
-      *count_host = 0;
-      return PSH_OK;
-    }
-    *count_host = static_cast<int>(host_counters[0]);
-    const unsigned got = std::min<unsigned>(host_counters[0], static_cast<unsigned>(capacity));
-    if (got) {
-      PSH_HIP(hipMemcpyAsync(coords_host, coords, static_cast<size_t>(got) * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-      PSH_HIP(hipMemcpyAsync(values_host, values, static_cast<size_t>(got) * sizeof(double), hipMemcpyDeviceToHost, s));
-      PSH_HIP(hipStreamSynchronize(s));
-    }
+  hipStream_t s = c.stream;
+  PSH_HIP(hipMemsetAsync(counters, 0, 2 * sizeof(unsigned), s));
+  auto blocks = [](size_t lines) { return dim3(static_cast<unsigned>((lines + kBlobThreads - 1) / kBlobThreads)); };
+  // maximum_filter1d along the image rows' index (axis 0 of scikit-image's (m, n, K) cube), the columns' (axis 1), the scales (axis 2)
+  hipLaunchKernelGGL(blob_max3_lines, blocks(static_cast<size_t>(K) * n), dim3(kBlobThreads), 0, s, cube_dev, cmax,
+                     static_cast<size_t>(K) * n, static_cast<size_t>(n), plane, m, static_cast<size_t>(n));
+  hipLaunchKernelGGL(blob_max3_lines, blocks(static_cast<size_t>(K) * m), dim3(kBlobThreads), 0, s, static_cast<const double *>(cmax), cmax,
+                     static_cast<size_t>(K) * m, static_cast<size_t>(1), static_cast<size_t>(n), n, static_cast<size_t>(1));
+  hipLaunchKernelGGL(blob_max3_lines, blocks(plane), dim3(kBlobThreads), 0, s, static_cast<const double *>(cmax), cmax, plane,
+                     plane, static_cast<size_t>(0), K, plane);
+  const unsigned grid = static_cast<unsigned>(std::min<size_t>((total + kBlobThreads - 1) / kBlobThreads, 8192));
+  hipLaunchKernelGGL(blob_collect, dim3(grid), dim3(kBlobThreads), 0, s, cube_dev, static_cast<const double *>(cmax), K, m, n, threshold,
+                     capacity, coords, values, counters);
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(host_counters, counters, sizeof(host_counters), hipMemcpyDeviceToHost, s));
+  PSH_HIP(hipStreamSynchronize(s));
+  if (host_counters[1] == 0u) {  // peak.py _get_peak_mask: "no peak for a trivial image"
+    *count_host = 0;
     return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  }
+  *count_host = static_cast<int>(host_counters[0]);
+  const unsigned got = std::min<unsigned>(host_counters[0], static_cast<unsigned>(capacity));
+  if (got) {
+    PSH_HIP(hipMemcpyAsync(coords_host, coords, static_cast<size_t>(got) * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    PSH_HIP(hipMemcpyAsync(values_host, values, static_cast<size_t>(got) * sizeof(double), hipMemcpyDeviceToHost, s));
+    PSH_HIP(hipStreamSynchronize(s));
+  }
+  return PSH_OK;
 }
 
 extern "C" int psh_blob_gather_dev(const double *plane_dev, int m, int n, const int *yx_host, int count, double *values_host) {
@@ -357,19 +347,14 @@ extern "C" int psh_blob_gather_dev(const double *plane_dev, int m, int n, const 
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const size_t ibytes = (static_cast<size_t>(count) * 2 * sizeof(int) + 255) & ~static_cast<size_t>(255);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, ibytes + static_cast<size_t>(count) * sizeof(double))) return rc;
-  int *yx = static_cast<int *>(blk);
-  double *vals = reinterpret_cast<double *>(static_cast<char *>(blk) + ibytes);
-  auto run = [&]() -> int {
-    PSH_HIP(hipMemcpyAsync(yx, yx_host, static_cast<size_t>(count) * 2 * sizeof(int), hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(blob_gather, dim3((count + 255) / 256), dim3(256), 0, c.stream, plane_dev, n, static_cast<const int *>(yx), count, vals);
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(values_host, vals, static_cast<size_t>(count) * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(ibytes + static_cast<size_t>(count) * sizeof(double))) return rc;
+  int *yx = blk.as<int>();
+  double *vals = blk.at<double>(ibytes);
+  PSH_HIP(hipMemcpyAsync(yx, yx_host, static_cast<size_t>(count) * 2 * sizeof(int), hipMemcpyHostToDevice, c.stream));
+  hipLaunchKernelGGL(blob_gather, dim3((count + 255) / 256), dim3(256), 0, c.stream, plane_dev, n, static_cast<const int *>(yx), count, vals);
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(values_host, vals, static_cast<size_t>(count) * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  return PSH_OK;
 }

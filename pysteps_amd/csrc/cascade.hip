@@ -153,15 +153,13 @@ __global__ __launch_bounds__(kRedThreads) void ar_iterate(const double *__restri
 
 // {mean, population std} of `planes` planes (declared in common.h: noise_adj.hip standardises with it too)
 int moments(const double *x_dev, int planes, size_t plane, double2 *stats_dev, hipStream_t stream) {
-  void *partial = nullptr;
-  if (int rc = psh_malloc(&partial, static_cast<size_t>(planes) * kRedBlocksF64 * sizeof(double2))) return rc;
+  psh::Scratch partial;
+  if (int rc = partial.alloc(static_cast<size_t>(planes) * kRedBlocksF64 * sizeof(double2))) return rc;
   hipLaunchKernelGGL(moments_partial, dim3(kRedBlocksF64, planes), dim3(kRedThreads), 0, stream, x_dev, plane,
-                     static_cast<double2 *>(partial));
-  hipLaunchKernelGGL(moments_final, dim3(planes), dim3(kRedThreads), 0, stream, static_cast<const double2 *>(partial),
+                     partial.as<double2>());
+  hipLaunchKernelGGL(moments_final, dim3(planes), dim3(kRedThreads), 0, stream, partial.as<const double2>(),
                      kRedBlocksF64, x_dev, plane, stats_dev);
-  const hipError_t e = hipGetLastError();
-  (void)psh_free(partial);
-  if (e != hipSuccess) return fail(PSH_EHIP, "moments launch failed: %s", hipGetErrorString(e));
+  PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
@@ -189,51 +187,46 @@ static int cascade_decompose_run(const double *field_dev, const double *weights_
   PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n, nc = static_cast<size_t>(n / 2 + 1);
   const size_t spec_bytes = static_cast<size_t>(m) * nc * sizeof(double2);
-  void *blk = nullptr;
+  psh::Scratch blk;
   // [spectrum | scratch of the inverse column pass | centred copy of the field (subtract_mean) | stats]
   const size_t stats_bytes = (static_cast<size_t>(nlevels) + 1) * sizeof(double2);
-  if (int rc = psh_malloc(&blk, 2 * spec_bytes + (subtract_mean ? plane * sizeof(double) : 0) + stats_bytes)) return rc;
-  char *base = static_cast<char *>(blk);
+  if (int rc = blk.alloc(2 * spec_bytes + (subtract_mean ? plane * sizeof(double) : 0) + stats_bytes)) return rc;
+  char *base = blk.as<char>();
   void *spec = base, *scratch = base + spec_bytes;
   double *centred = reinterpret_cast<double *>(base + 2 * spec_bytes);
   double2 *stats = reinterpret_cast<double2 *>(base + 2 * spec_bytes + (subtract_mean ? plane * sizeof(double) : 0));
-  auto run = [&]() -> int {
-    const double *src = field_dev;
-    if (subtract_mean) {  // decomposition.py:199-202
-      PSH_HIP(hipMemcpyAsync(centred, field_dev, plane * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
-      if (int rc = psh::moments(centred, 1, plane, stats + nlevels, c.stream)) return rc;
-      hipLaunchKernelGGL(psh::standardise, dim3(psh::kRedBlocksF64, 1), dim3(psh::kRedThreads), 0, c.stream, centred,
-                         plane, stats + nlevels, 1);
-      src = centred;
-    }
-    if (int rc = psh_fft_rfft2_dev(src, m, n, spec)) return rc;
-    for (int k = 0; k < nlevels; ++k) {  // :210-215: field_fft * weights_2d[k], back to the spatial domain
-      if (int rc = psh::fft_irfft2_weighted(spec, weights_dev + static_cast<size_t>(k) * m * nc, m, n,
-                                            levels_dev + static_cast<size_t>(k) * plane, scratch))
-        return rc;
-    }
-    if (levels_only) return PSH_OK;
-    if (int rc = psh::moments(levels_dev, nlevels, plane, stats, c.stream)) return rc;  // :217-232
-    if (stats_out_dev)
-      PSH_HIP(hipMemcpyAsync(stats_out_dev, stats, static_cast<size_t>(nlevels) * sizeof(double2), hipMemcpyDeviceToDevice, c.stream));
-    if (normalize)
-      hipLaunchKernelGGL(psh::standardise, dim3(psh::kRedBlocksF64, nlevels), dim3(psh::kRedThreads), 0, c.stream,
-                         levels_dev, plane, stats, 0);
-    PSH_HIP(hipGetLastError());
-    if (!means_host) return PSH_OK;  // resident member loop: nobody on the host needs the statistics, no wait
-    double2 host[65];
-    PSH_HIP(hipMemcpyAsync(host, stats, stats_bytes, hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    for (int k = 0; k < nlevels; ++k) {
-      means_host[k] = host[k].x;
-      stds_host[k] = host[k].y;
-    }
-    if (field_mean_host) *field_mean_host = subtract_mean ? host[nlevels].x : 0.0;
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  const double *src = field_dev;
+  if (subtract_mean) {  // decomposition.py:199-202
+    PSH_HIP(hipMemcpyAsync(centred, field_dev, plane * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+    if (int rc = psh::moments(centred, 1, plane, stats + nlevels, c.stream)) return rc;
+    hipLaunchKernelGGL(psh::standardise, dim3(psh::kRedBlocksF64, 1), dim3(psh::kRedThreads), 0, c.stream, centred,
+                       plane, stats + nlevels, 1);
+    src = centred;
+  }
+  if (int rc = psh_fft_rfft2_dev(src, m, n, spec)) return rc;
+  for (int k = 0; k < nlevels; ++k) {  // :210-215: field_fft * weights_2d[k], back to the spatial domain
+    if (int rc = psh::fft_irfft2_weighted(spec, weights_dev + static_cast<size_t>(k) * m * nc, m, n,
+                                          levels_dev + static_cast<size_t>(k) * plane, scratch))
+      return rc;
+  }
+  if (levels_only) return PSH_OK;
+  if (int rc = psh::moments(levels_dev, nlevels, plane, stats, c.stream)) return rc;  // :217-232
+  if (stats_out_dev)
+    PSH_HIP(hipMemcpyAsync(stats_out_dev, stats, static_cast<size_t>(nlevels) * sizeof(double2), hipMemcpyDeviceToDevice, c.stream));
+  if (normalize)
+    hipLaunchKernelGGL(psh::standardise, dim3(psh::kRedBlocksF64, nlevels), dim3(psh::kRedThreads), 0, c.stream,
+                       levels_dev, plane, stats, 0);
+  PSH_HIP(hipGetLastError());
+  if (!means_host) return PSH_OK;  // resident member loop: nobody on the host needs the statistics, no wait
+  double2 host[65];
+  PSH_HIP(hipMemcpyAsync(host, stats, stats_bytes, hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  for (int k = 0; k < nlevels; ++k) {
+    means_host[k] = host[k].x;
+    stds_host[k] = host[k].y;
+  }
+  if (field_mean_host) *field_mean_host = subtract_mean ? host[nlevels].x : 0.0;
+  return PSH_OK;
 }
 
 extern "C" int psh_cascade_decompose_dev(const double *field_dev, const double *weights_dev, int nlevels, int m,
@@ -297,22 +290,17 @@ extern "C" int psh_noise_filter_dev(const double *white_dev, const double *filte
   PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n;
   const size_t spec_bytes = static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 2 * spec_bytes + sizeof(double2))) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(2 * spec_bytes + sizeof(double2))) return rc;
+  char *base = blk.as<char>();
   double2 *stats = reinterpret_cast<double2 *>(base + 2 * spec_bytes);
-  auto run = [&]() -> int {
-    if (int rc = psh_fft_rfft2_dev(white_dev, m, n, base)) return rc;                                  // :423
-    if (int rc = psh::fft_irfft2_weighted(base, filter_dev, m, n, out_dev, base + spec_bytes)) return rc;  // :427-431
-    if (int rc = psh::moments(out_dev, 1, plane, stats, c.stream)) return rc;
-    hipLaunchKernelGGL(psh::standardise, dim3(psh::kRedBlocksF64, 1), dim3(psh::kRedThreads), 0, c.stream, out_dev,
-                       plane, stats, 0);                                                                // :432
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  if (int rc = psh_fft_rfft2_dev(white_dev, m, n, base)) return rc;                                  // :423
+  if (int rc = psh::fft_irfft2_weighted(base, filter_dev, m, n, out_dev, base + spec_bytes)) return rc;  // :427-431
+  if (int rc = psh::moments(out_dev, 1, plane, stats, c.stream)) return rc;
+  hipLaunchKernelGGL(psh::standardise, dim3(psh::kRedBlocksF64, 1), dim3(psh::kRedThreads), 0, c.stream, out_dev,
+                     plane, stats, 0);                                                                // :432
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 extern "C" int psh_ar_iterate_dev(const double *x_dev, int nt, size_t plane, const double *phi_host, int p,

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "../../include/pysteps_hip.h"
+#include "scratch.h"
 
 // Device-side assertions of the debug build (python -m pysteps_amd.build --debug: -O1 -g -DPSH_DEBUG): compiled out
 // of the product.  A violated one prints file:line and traps the kernel; the host sees the launch fail.
@@ -81,6 +82,15 @@ int const_slot(float **host, const float **dev);
     if (!::psh::ctx().ready)                                                     \
       return ::psh::fail(PSH_ENOTINIT, "psh_init() has not been called");        \
   } while (0)
+
+// Element-type dispatch of the entry points that take `const void *` plus an "is float64" flag: f is called with the
+// pointer as const double * or const float *.  Two-field entry points nest two calls.
+template <class F> auto with_real(const void *p, bool f64, F &&f) {
+  return f64 ? f(static_cast<const double *>(p)) : f(static_cast<const float *>(p));
+}
+template <class F> auto with_real(void *p, bool f64, F &&f) {
+  return f64 ? f(static_cast<double *>(p)) : f(static_cast<float *>(p));
+}
 
 int check_semilag(int m, int n, int T, int n_iter, int order_and_mode);
 

@@ -285,27 +285,19 @@ extern "C" int psh_darts_nonfinite_dev(const void *frames_dev, int f32, size_t c
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, sizeof(int))) return rc;
-  int *flag = static_cast<int *>(blk);
-  auto run = [&]() -> int {
-    PSH_HIP(hipMemsetAsync(flag, 0, sizeof(int), c.stream));
-    if (count) {
-      if (f32)
-        hipLaunchKernelGGL(darts_nonfinite<float>, dim3(blocks_for(count)), dim3(kDartsThreads), 0, c.stream,
-                           static_cast<const float *>(frames_dev), count, flag);
-      else
-        hipLaunchKernelGGL(darts_nonfinite<double>, dim3(blocks_for(count)), dim3(kDartsThreads), 0, c.stream,
-                           static_cast<const double *>(frames_dev), count, flag);
-      PSH_HIP(hipGetLastError());
-    }
-    PSH_HIP(hipMemcpyAsync(flag_host, flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(sizeof(int))) return rc;
+  int *flag = blk.as<int>();
+  PSH_HIP(hipMemsetAsync(flag, 0, sizeof(int), c.stream));
+  if (count) {
+    with_real(frames_dev, !f32, [&](auto *frames) {
+      hipLaunchKernelGGL(darts_nonfinite, dim3(blocks_for(count)), dim3(kDartsThreads), 0, c.stream, frames, count, flag);
+    });
+    PSH_HIP(hipGetLastError());
+  }
+  PSH_HIP(hipMemcpyAsync(flag_host, flag, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  return PSH_OK;
 }
 
 extern "C" int psh_darts_band_dev(const void *frames_dev, int f32, int T, int m, int n, int ky, int kx, int nt, void *cube_dev) {
@@ -326,39 +318,34 @@ extern "C" int psh_darts_band_dev(const void *frames_dev, int f32, int T, int m,
   const size_t spec_bytes = static_cast<size_t>(m) * nc * sizeof(double2);
   const size_t wide_bytes = f32 ? plane * sizeof(double) : 0;
   const size_t planes_bytes = static_cast<size_t>(T) * P * sizeof(double2);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, spec_bytes + wide_bytes + planes_bytes)) return rc;
-  double2 *spec = static_cast<double2 *>(blk);
-  double *wide = reinterpret_cast<double *>(reinterpret_cast<char *>(blk) + spec_bytes);
-  double2 *planes = reinterpret_cast<double2 *>(reinterpret_cast<char *>(blk) + spec_bytes + wide_bytes);
-  auto run = [&]() -> int {
-    for (int t = 0; t < T; ++t) {
-      const double *frame;
-      if (f32) {
-        if (int rc = psh_convert_dev(static_cast<const float *>(frames_dev) + t * plane, wide, plane, 1)) return rc;
-        frame = wide;
-      } else {
-        frame = static_cast<const double *>(frames_dev) + t * plane;
-      }
-      if (int rc = psh_fft_rfft2_dev(frame, m, n, spec)) return rc;
-      hipLaunchKernelGGL(darts_gather, dim3((P + kDartsThreads - 1) / kDartsThreads), dim3(kDartsThreads), 0, c.stream, spec, m, n,
-                         ky, kx, planes + t * P);
-      PSH_HIP(hipGetLastError());
+  psh::Scratch blk;
+  if (int rc = blk.alloc(spec_bytes + wide_bytes + planes_bytes)) return rc;
+  double2 *spec = blk.as<double2>();
+  double *wide = blk.at<double>(spec_bytes);
+  double2 *planes = blk.at<double2>(spec_bytes + wide_bytes);
+  for (int t = 0; t < T; ++t) {
+    const double *frame;
+    if (f32) {
+      if (int rc = psh_convert_dev(static_cast<const float *>(frames_dev) + t * plane, wide, plane, 1)) return rc;
+      frame = wide;
+    } else {
+      frame = static_cast<const double *>(frames_dev) + t * plane;
     }
-    TimeTwiddles tw;
-    const long double step = -2.0L * 3.14159265358979323846264338327950288L / static_cast<long double>(T);
-    for (int j = 0; j < kDartsMaxFrames; ++j) {
-      const long double a = step * static_cast<long double>(j < T ? j : 0);
-      tw.w[j] = make_double2(static_cast<double>(cosl(a)), static_cast<double>(sinl(a)));
-    }
-    hipLaunchKernelGGL(darts_time_dft, dim3((P + kDartsThreads - 1) / kDartsThreads), dim3(kDartsThreads), 0, c.stream,
-                       static_cast<const double2 *>(planes), T, static_cast<int>(P), nt, tw, static_cast<double2 *>(cube_dev));
+    if (int rc = psh_fft_rfft2_dev(frame, m, n, spec)) return rc;
+    hipLaunchKernelGGL(darts_gather, dim3((P + kDartsThreads - 1) / kDartsThreads), dim3(kDartsThreads), 0, c.stream, spec, m, n,
+                       ky, kx, planes + t * P);
     PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  }
+  TimeTwiddles tw;
+  const long double step = -2.0L * 3.14159265358979323846264338327950288L / static_cast<long double>(T);
+  for (int j = 0; j < kDartsMaxFrames; ++j) {
+    const long double a = step * static_cast<long double>(j < T ? j : 0);
+    tw.w[j] = make_double2(static_cast<double>(cosl(a)), static_cast<double>(sinl(a)));
+  }
+  hipLaunchKernelGGL(darts_time_dft, dim3((P + kDartsThreads - 1) / kDartsThreads), dim3(kDartsThreads), 0, c.stream,
+                     static_cast<const double2 *>(planes), T, static_cast<int>(P), nt, tw, static_cast<double2 *>(cube_dev));
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 extern "C" int psh_darts_gram_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx, double cy, double cx, void *out_host) {
@@ -375,22 +362,17 @@ extern "C" int psh_darts_gram_dev(const void *cube_dev, int Nt, int Ny, int Nx, 
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, (static_cast<size_t>(nblocks) + 1) * nout * sizeof(double2))) return rc;
-  double2 *slab = static_cast<double2 *>(blk), *out = slab + static_cast<size_t>(nblocks) * nout;
-  auto run = [&]() -> int {
-    hipLaunchKernelGGL(darts_gram_partial, dim3(nblocks, groups), dim3(kDartsThreads), 0, c.stream, a, rows_per_block, slab);
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(darts_gram_final, dim3((nout + kDartsThreads - 1) / kDartsThreads), dim3(kDartsThreads), 0, c.stream,
-                       static_cast<const double2 *>(slab), nblocks, nout, out);
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(nout) * sizeof(double2), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc((static_cast<size_t>(nblocks) + 1) * nout * sizeof(double2))) return rc;
+  double2 *slab = blk.as<double2>(), *out = slab + static_cast<size_t>(nblocks) * nout;
+  hipLaunchKernelGGL(darts_gram_partial, dim3(nblocks, groups), dim3(kDartsThreads), 0, c.stream, a, rows_per_block, slab);
+  PSH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(darts_gram_final, dim3((nout + kDartsThreads - 1) / kDartsThreads), dim3(kDartsThreads), 0, c.stream,
+                     static_cast<const double2 *>(slab), nblocks, nout, out);
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(out_host, out, static_cast<size_t>(nout) * sizeof(double2), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  return PSH_OK;
 }
 
 extern "C" int psh_darts_rows_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx, double cy, double cx, void *M_dev,
@@ -430,26 +412,19 @@ extern "C" int psh_darts_synth_dev(const int *ky_host, const int *kx_host, const
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(nb) * (n + 2 * static_cast<size_t>(m)) * sizeof(double2))) return rc;
-  double2 *ex = static_cast<double2 *>(blk), *py = ex + static_cast<size_t>(nb) * n;
-  auto run = [&]() -> int {
-    const int side = std::max(m, n);
-    hipLaunchKernelGGL(darts_synth_tables, dim3((side + kDartsThreads - 1) / kDartsThreads, nb), dim3(kDartsThreads), 0, c.stream,
-                       bins, nb, m, n, ex, py);
-    PSH_HIP(hipGetLastError());
-    const dim3 grid((n + kDartsThreads - 1) / kDartsThreads, m);
-    const double scale = 1.0 / (static_cast<double>(m) * static_cast<double>(n));
-    if (f32)
-      hipLaunchKernelGGL(darts_synth<float>, grid, dim3(kDartsThreads), 0, c.stream, static_cast<const double2 *>(ex),
-                         static_cast<const double2 *>(py), nb, m, n, scale, static_cast<float *>(out_dev));
-    else
-      hipLaunchKernelGGL(darts_synth<double>, grid, dim3(kDartsThreads), 0, c.stream, static_cast<const double2 *>(ex),
-                         static_cast<const double2 *>(py), nb, m, n, scale, static_cast<double *>(out_dev));
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(nb) * (n + 2 * static_cast<size_t>(m)) * sizeof(double2))) return rc;
+  double2 *ex = blk.as<double2>(), *py = ex + static_cast<size_t>(nb) * n;
+  const int side = std::max(m, n);
+  hipLaunchKernelGGL(darts_synth_tables, dim3((side + kDartsThreads - 1) / kDartsThreads, nb), dim3(kDartsThreads), 0, c.stream,
+                     bins, nb, m, n, ex, py);
+  PSH_HIP(hipGetLastError());
+  const dim3 grid((n + kDartsThreads - 1) / kDartsThreads, m);
+  const double scale = 1.0 / (static_cast<double>(m) * static_cast<double>(n));
+  with_real(out_dev, !f32, [&](auto *out) {
+    hipLaunchKernelGGL(darts_synth, grid, dim3(kDartsThreads), 0, c.stream, static_cast<const double2 *>(ex),
+                       static_cast<const double2 *>(py), nb, m, n, scale, out);
+  });
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }

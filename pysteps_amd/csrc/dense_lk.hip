@@ -19,22 +19,9 @@
 
 namespace {
 
-// RAII for psh_malloc blocks (stream-ordered free)
 __global__ __launch_bounds__(256) void zero_dwords(unsigned *__restrict__ p, size_t n) {
   for (size_t i = threadIdx.x; i < n; i += 256) p[i] = 0u;
 }
-
-struct DevBlock {
-  void *p = nullptr;
-  ~DevBlock() {
-    if (p) (void)psh_free(p);
-  }
-  int alloc(size_t bytes) { return psh_malloc(&p, bytes); }
-  template <class T>
-  T *as() const {
-    return static_cast<T *>(p);
-  }
-};
 
 }  // namespace
 
@@ -78,7 +65,7 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
   // beside the corner chain of frame t (which needs nothing of it): its passes stream the frame
   // through HBM while the Shi-Tomasi response is bound by the VALUs and the ordered walk is a single
   // workgroup; the pyramids of the pair follow on the same side stream, the tracker joins both.
-  std::vector<DevBlock> clean(nframes), trk(nframes), feat(nframes), stats(nframes);
+  std::vector<psh::Scratch> clean(nframes), trk(nframes), feat(nframes), stats(nframes);
   const bool f64 = prm->frames_f64 != 0;
   const size_t frame_bytes = plane * (f64 ? sizeof(double) : sizeof(float));
   auto frame_ptr = [&](int t) { return reinterpret_cast<const char *>(frames_dev) + static_cast<size_t>(t) * frame_bytes; };
@@ -107,7 +94,7 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
   const size_t off_uv = cap * 16, off_cnt = 2 * cap * 16, off_fl = off_cnt + 256;
   const size_t slot_bytes = (psh::lk_slot_bytes() + 255) & ~static_cast<size_t>(255);
   const size_t off_slots = (off_fl + cap + 255) & ~static_cast<size_t>(255);
-  DevBlock pool;
+  psh::Scratch pool;
   if (int rc = pool.alloc(off_slots + slot_bytes * nframes)) return rc;
   char *pbase = pool.as<char>();
   double *d_pxy = reinterpret_cast<double *>(pbase), *d_puv = reinterpret_cast<double *>(pbase + off_uv);
@@ -119,7 +106,7 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
                      (off_slots + slot_bytes * nframes - off_cnt) / 4);
   PSH_HIP(hipGetLastError());
   auto frame_slots = [&](int t) { return reinterpret_cast<unsigned *>(pbase + off_slots + slot_bytes * t); };
-  DevBlock ws_main, ws_side;  // allocated before any fork, released after the last join
+  psh::Scratch ws_main, ws_side;  // allocated before any fork, released after the last join
   if (int rc = ws_main.alloc(psh::lk_prepare_ws_bytes(m, n, f64))) return rc;
   if (nframes > 1)
     if (int rc = ws_side.alloc(psh::lk_prepare_ws_bytes(m, n, f64))) return rc;
@@ -130,7 +117,7 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
                               f64 ? nullptr : frame_slots(t), f64 ? nullptr : clean[t].as<unsigned long long>());
   };
   auto nan_pattern = [&](int t) { return f64 ? clean[t].as<float>() : reinterpret_cast<const float *>(frame_ptr(t)); };
-  if (int rc = prepare(0, c.stream, ws_main.p)) return rc;
+  if (int rc = prepare(0, c.stream, ws_main.as<void>())) return rc;
 
   // ---- per frame pair: features, tracking, pooling (:207-242) ---------------------------
   // Everything stays on the device: the corners are ordered and accepted by corner_order
@@ -138,10 +125,10 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
   // tracks of all pairs are pooled by lk_pool_append and the outlier test reads its sample count
   // from device memory.  The dense estimate is one chain of kernel launches; only dense=False
   // (sparse vectors for the caller) ends with a copy to the host.
-  DevBlock corners;  // [int count | pad to 256 | max_corners (x, y) float32], reused pair after pair
+  psh::Scratch corners;  // [int count | pad to 256 | max_corners (x, y) float32], reused pair after pair
   if (int rc = corners.alloc(256 + static_cast<size_t>(prm->max_corners) * 2 * sizeof(float))) return rc;
   int *d_npts = corners.as<int>();
-  float *d_pts = reinterpret_cast<float *>(corners.as<char>() + 256);
+  float *d_pts = corners.at<float>(256);
   for (int t = 0; t + 1 < nframes; ++t) {
     // side stream: the next frame's passes, then the pyramids of the pair (they only need the uint8
     // renderings); main stream: the corner chain of this frame; joined before the tracker.  The corner chain is
@@ -153,8 +140,8 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
     // (the pyramids' storage is taken NOW: a block the allocator hands out after the corner chain is queued may be
     // one that chain just gave back, and the side stream does not wait for the chain)
     const size_t pyr_bytes = psh::lk_pyramids_bytes(m, n, prm->win_w, prm->win_h, prm->max_level);
-    void *pyr_block = nullptr;
-    if (int rc = psh_malloc(&pyr_block, pyr_bytes)) {
+    psh::Scratch pyr_block;  // handed to the pyramid set below
+    if (int rc = pyr_block.alloc(pyr_bytes)) {
       (void)psh::side_end();
       return rc;
     }
@@ -163,9 +150,8 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
                                              stats[t].as<float>(), m, n, prm->block_size, prm->buffer_mask,
                                              prm->quality_level, prm->min_distance, prm->max_corners, d_pts, d_npts,
                                              nullptr, nullptr, trace ? walk_stats : nullptr, frame_slots(t));
-    if (int rc = prepare(t + 1, side, ws_side.p)) {
+    if (int rc = prepare(t + 1, side, ws_side.as<void>())) {
       (void)psh::side_end();
-      (void)psh_free(pyr_block);
       return rc;
     }
     struct Fork {
@@ -173,7 +159,7 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
       int rc;
     } fork{nullptr, PSH_OK};
     // queued behind the frame passes on the side stream (forked above, after this frame's passes on the main stream)
-    fork.rc = psh::lk_pyramids_on_side(side, pyr_block, pyr_bytes, trk[t].as<unsigned char>(), trk[t + 1].as<unsigned char>(),
+    fork.rc = psh::lk_pyramids_on_side(side, pyr_block.release(), pyr_bytes, trk[t].as<unsigned char>(), trk[t + 1].as<unsigned char>(),
                                        m, n, prm->win_w, prm->win_h, prm->max_level, &fork.pyr);
     const int rcj = psh::side_end();
     void *pyr = fork.pyr;
@@ -200,11 +186,11 @@ extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, 
   if (field_dev) {
     // ---- dense field: filter, declustering (:264-265), interpolator preamble and IDW (:272-274),
     // all from device memory (vectors_finish writes the sample list and its length) -------------
-    DevBlock samples;
+    psh::Scratch samples;
     const size_t sbytes = cap * 2 * sizeof(float);
     if (int rc = samples.alloc(2 * sbytes + 256)) return rc;
     float *d_xy = samples.as<float>(), *d_uv = d_xy + cap * 2;
-    psh::IdwDyn *d_dyn = reinterpret_cast<psh::IdwDyn *>(samples.as<char>() + 2 * sbytes);
+    psh::IdwDyn *d_dyn = samples.at<psh::IdwDyn>(2 * sbytes);
     PSH_HIP(psh::launch_vectors_finish(d_pxy, d_puv, d_pfl, d_pcnt, capacity_dev, prm->decl_scale, m, n, d_xy, d_uv,
                                        d_dyn, c.stream));
     if (int rc = psh::idw_resident(d_xy, d_uv, capacity_dev, d_dyn, m, n, prm->idw_k, prm->idw_power,

@@ -308,15 +308,11 @@ extern "C" int psh_detcat_counts_dev(const void *fct_dev, int fct_f64, const voi
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemsetAsync(out_dev, 0, static_cast<size_t>(K) * n_thresholds * 4 * sizeof(unsigned long long), c.stream));
-  if (fct_f64)
-    return obs_f64 ? run_cat(static_cast<const double *>(fct_dev), static_cast<const double *>(obs_dev), obs_shared, K, npix,
-                             thr_fct_host, thr_obs_host, n_thresholds, out_dev, c.stream)
-                   : run_cat(static_cast<const double *>(fct_dev), static_cast<const float *>(obs_dev), obs_shared, K, npix,
-                             thr_fct_host, thr_obs_host, n_thresholds, out_dev, c.stream);
-  return obs_f64 ? run_cat(static_cast<const float *>(fct_dev), static_cast<const double *>(obs_dev), obs_shared, K, npix,
-                           thr_fct_host, thr_obs_host, n_thresholds, out_dev, c.stream)
-                 : run_cat(static_cast<const float *>(fct_dev), static_cast<const float *>(obs_dev), obs_shared, K, npix,
-                           thr_fct_host, thr_obs_host, n_thresholds, out_dev, c.stream);
+  return with_real(fct_dev, fct_f64 != 0, [&](auto *fct) {
+    return with_real(obs_dev, obs_f64 != 0, [&](auto *obs) {
+      return run_cat(fct, obs, obs_shared, K, npix, thr_fct_host, thr_obs_host, n_thresholds, out_dev, c.stream);
+    });
+  });
 }
 
 extern "C" int psh_detcont_sums_dev(const void *fct_dev, int fct_f64, const void *obs_dev, int obs_f64, int obs_shared, int K,
@@ -330,20 +326,12 @@ extern "C" int psh_detcont_sums_dev(const void *fct_dev, int fct_f64, const void
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(K) * det_groups(npix) * sizeof(DetPartial))) return rc;
-  DetPartial *part = static_cast<DetPartial *>(blk);
-  int rc;
-  if (fct_f64)
-    rc = obs_f64 ? run_cont(static_cast<const double *>(fct_dev), static_cast<const double *>(obs_dev), obs_shared, K, npix,
-                            conditioning, thr_fct, thr_obs, part, counts_dev, sums_dev, c.stream)
-                 : run_cont(static_cast<const double *>(fct_dev), static_cast<const float *>(obs_dev), obs_shared, K, npix,
-                            conditioning, thr_fct, thr_obs, part, counts_dev, sums_dev, c.stream);
-  else
-    rc = obs_f64 ? run_cont(static_cast<const float *>(fct_dev), static_cast<const double *>(obs_dev), obs_shared, K, npix,
-                            conditioning, thr_fct, thr_obs, part, counts_dev, sums_dev, c.stream)
-                 : run_cont(static_cast<const float *>(fct_dev), static_cast<const float *>(obs_dev), obs_shared, K, npix,
-                            conditioning, thr_fct, thr_obs, part, counts_dev, sums_dev, c.stream);
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(K) * det_groups(npix) * sizeof(DetPartial))) return rc;
+  DetPartial *part = blk.as<DetPartial>();
+  return with_real(fct_dev, fct_f64 != 0, [&](auto *fct) {
+    return with_real(obs_dev, obs_f64 != 0, [&](auto *obs) {
+      return run_cont(fct, obs, obs_shared, K, npix, conditioning, thr_fct, thr_obs, part, counts_dev, sums_dev, c.stream);
+    });
+  });
 }

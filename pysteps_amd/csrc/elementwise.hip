@@ -204,19 +204,13 @@ hipError_t launch_convert_f32_f64(const float *in, double *out, size_t n, hipStr
 int field_stats_full(const float *in_dev, size_t n, FieldStats *st) {
   Context &c = ctx();
   constexpr int kBlocks = 1024;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, kStatFields * kBlocks * sizeof(float))) return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(kStatFields * kBlocks * sizeof(float))) return rc;
   static thread_local float h[kStatFields * kBlocks];
-  auto run = [&]() -> int {
-    hipLaunchKernelGGL(field_stats, dim3(kBlocks), dim3(256), 0, c.stream, in_dev, n, static_cast<float *>(blk));
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(h, blk, sizeof(h), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  if (rc) return rc;
+  hipLaunchKernelGGL(field_stats, dim3(kBlocks), dim3(256), 0, c.stream, in_dev, n, blk.as<float>());
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(h, blk.as<float>(), sizeof(h), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
   FieldStats r;
   for (int b = 0; b < kBlocks; ++b) {
     const float *o = h + kStatFields * b;
@@ -234,19 +228,13 @@ int field_stats_full(const float *in_dev, size_t n, FieldStats *st) {
 int field_stats_full_f64(const double *in_dev, size_t n, FieldStats *st) {
   Context &c = ctx();
   constexpr int kBlocks = 1024;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, kStatFields * kBlocks * sizeof(double))) return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(kStatFields * kBlocks * sizeof(double))) return rc;
   static thread_local double h[kStatFields * kBlocks];
-  auto run = [&]() -> int {
-    hipLaunchKernelGGL(field_stats_f64, dim3(kBlocks), dim3(256), 0, c.stream, in_dev, n, static_cast<double *>(blk));
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(h, blk, sizeof(h), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  if (rc) return rc;
+  hipLaunchKernelGGL(field_stats_f64, dim3(kBlocks), dim3(256), 0, c.stream, in_dev, n, blk.as<double>());
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(h, blk.as<double>(), sizeof(h), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
   FieldStats r;
   for (int b = 0; b < kBlocks; ++b) {
     const double *o = h + kStatFields * b;
@@ -288,21 +276,14 @@ extern "C" int psh_count_above_dev(const float *in_dev, size_t n, double thresho
   if (nanmin_out) *nanmin_out = lowest;
   // threshold NaN = "use the minimum of the field" (precip_thr=None, check_norain.py:46-47)
   const double thr = threshold != threshold ? lowest : threshold;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, sizeof(unsigned long long))) return rc;
-  unsigned long long h = 0;
-  auto run = [&]() -> int {
-    PSH_HIP(hipMemsetAsync(blk, 0, sizeof(unsigned long long), c.stream));
-    hipLaunchKernelGGL(psh::count_above, dim3(c.cu_count * 8), dim3(256), 0, c.stream, in_dev, n, thr,
-                       static_cast<unsigned long long *>(blk));
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(&h, blk, sizeof(h), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  if (rc) return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(sizeof(unsigned long long))) return rc;
+  unsigned long long *count = blk.as<unsigned long long>(), h = 0;
+  PSH_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), c.stream));
+  hipLaunchKernelGGL(psh::count_above, dim3(c.cu_count * 8), dim3(256), 0, c.stream, in_dev, n, thr, count);
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(&h, count, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
   *count_out = static_cast<double>(h);
   return PSH_OK;
 }

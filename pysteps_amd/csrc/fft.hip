@@ -643,8 +643,8 @@ int launch_cols(bool inverse, const double2 *in, const Dft &d, int nc, double sc
   // 4096, 10-25 % slower at 1024 / 2048 (PYSTEPS_HIP_FFT_FOURSTEP=2 takes it from 1024 points on)
   if (four_step && !d.chirp && d.logm >= (four_step == 2 ? 10 : 13)) {
     // two sweeps over column tiles (fft_cols_step) through a block of the same size
-    void *tmp = nullptr;
-    if (int rc = psh_malloc(&tmp, static_cast<size_t>(len) * nc * sizeof(double2))) return rc;
+    psh::Scratch tmp;  // freed stream-ordered behind the sweeps
+    if (int rc = tmp.alloc(static_cast<size_t>(len) * nc * sizeof(double2))) return rc;
     const int log1 = d.logm / 2, log2_ = d.logm - log1;
     auto sweep = [&](auto kernel, int lc, int lt, int logl, int sequences, const double2 *src, double2 *dst, double sc,
                      const double *w) -> int {
@@ -662,7 +662,7 @@ int launch_cols(bool inverse, const double2 *in, const Dft &d, int nc, double sc
       return PSH_OK;
     };
     int rc = PSH_OK;
-    double2 *mid = static_cast<double2 *>(tmp);
+    double2 *mid = tmp.as<double2>();
 #define PSH_STEPS(LC, LT)                                                                                               \
   rc = inverse ? sweep(fft_cols_step<true, 0, LC, LT>, LC, LT, log2_, 1 << log1, in, mid, 1.0, weights)                 \
                : sweep(fft_cols_step<false, 0, LC, LT>, LC, LT, log2_, 1 << log1, in, mid, 1.0, weights);               \
@@ -673,7 +673,6 @@ int launch_cols(bool inverse, const double2 *in, const Dft &d, int nc, double sc
     // measured within 4 % of each other (profiles/r03/i_fft_column_pass_probe.txt), this one the fastest at 8192 points
     PSH_STEPS(4, 11);
 #undef PSH_STEPS
-    (void)psh_free(tmp);  // stream-ordered
     return rc;
   }
   // development knobs (tools/fft_quick.py): columns per workgroup / threads per workgroup of this pass
@@ -763,11 +762,9 @@ extern "C" int psh_fft_irfft2_dev(const void *in_dev, int m, int n, double *out_
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *scratch = nullptr;
-  if (int rc = psh_malloc(&scratch, static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2))) return rc;
-  const int rc = psh::fft_irfft2_weighted(in_dev, nullptr, m, n, out_dev, scratch);
-  (void)psh_free(scratch);  // stream-ordered
-  return rc;
+  psh::Scratch scratch;
+  if (int rc = scratch.alloc(static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2))) return rc;
+  return psh::fft_irfft2_weighted(in_dev, nullptr, m, n, out_dev, scratch.as<void>());
 }
 
 // ... and np.min of the result as the order-preserving key psh_steps_mask_dev reads (what psh_field_min_key_dev
@@ -780,12 +777,10 @@ extern "C" int psh_fft_irfft2_min_dev(const void *in_dev, int m, int n, double *
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *scratch = nullptr;
-  if (int rc = psh_malloc(&scratch, static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2))) return rc;
+  psh::Scratch scratch;
+  if (int rc = scratch.alloc(static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2))) return rc;
   PSH_HIP(hipMemsetAsync(min_key_dev, 0xff, sizeof(unsigned long long), c.stream));
-  const int rc = psh::fft_irfft2_weighted(in_dev, nullptr, m, n, out_dev, scratch, min_key_dev);
-  (void)psh_free(scratch);  // stream-ordered
-  return rc;
+  return psh::fft_irfft2_weighted(in_dev, nullptr, m, n, out_dev, scratch.as<void>(), min_key_dev);
 }
 
 // numpy.fft.fft2 / ifft2 of an (m, n) complex128 array (in_dev == out_dev allowed)

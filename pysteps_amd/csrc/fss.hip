@@ -304,27 +304,17 @@ extern "C" int psh_fss_sums_dev(const void *fct_dev, int fct_f64, const void *ob
   const size_t plane_bytes = static_cast<size_t>(m) * (static_cast<size_t>(n) + 1) * sizeof(uint32_t);
   size_t batch = kFssPrefixBytes / plane_bytes;
   batch = batch < 1 ? 1 : (batch > static_cast<size_t>(K) ? K : batch);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, plane_bytes * (batch + (obs_shared ? 1 : 0)))) return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(plane_bytes * (batch + (obs_shared ? 1 : 0)))) return rc;
   FssCall call;
   call.K = K, call.m = m, call.n = n, call.nthr = n_thresholds, call.nsc = n_scales, call.obs_shared = obs_shared ? 1 : 0;
   call.thr_f = thr_fct_host, call.thr_o = thr_obs_host, call.scales = scales;
-  call.prefix = static_cast<uint32_t *>(blk);
+  call.prefix = blk.as<uint32_t>();
   call.obs_prefix = call.prefix + batch * (plane_bytes / sizeof(uint32_t));
   call.batch = static_cast<int>(batch);
   call.out = out_dev;
-  int rc = PSH_OK;
-  const hipError_t e =
-      hipMemsetAsync(out_dev, 0, static_cast<size_t>(K) * n_thresholds * n_scales * 3 * sizeof(unsigned long long), c.stream);
-  if (e != hipSuccess) {
-    rc = fail(PSH_EHIP, "fss: hipMemsetAsync failed: %s", hipGetErrorString(e));
-  } else if (fct_f64) {
-    rc = obs_f64 ? run(call, static_cast<const double *>(fct_dev), static_cast<const double *>(obs_dev), c.stream)
-                 : run(call, static_cast<const double *>(fct_dev), static_cast<const float *>(obs_dev), c.stream);
-  } else {
-    rc = obs_f64 ? run(call, static_cast<const float *>(fct_dev), static_cast<const double *>(obs_dev), c.stream)
-                 : run(call, static_cast<const float *>(fct_dev), static_cast<const float *>(obs_dev), c.stream);
-  }
-  (void)psh_free(blk);
-  return rc;
+  PSH_HIP(hipMemsetAsync(out_dev, 0, static_cast<size_t>(K) * n_thresholds * n_scales * 3 * sizeof(unsigned long long), c.stream));
+  return with_real(fct_dev, fct_f64 != 0, [&](auto *fct) {
+    return with_real(obs_dev, obs_f64 != 0, [&](auto *obs) { return run(call, fct, obs, c.stream); });
+  });
 }

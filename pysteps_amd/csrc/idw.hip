@@ -1005,12 +1005,10 @@ extern "C" int psh_idw_dev(const float *xy_dev, const float *values_dev, int L, 
   a.offset = static_cast<float>(dist_offset);
   a.dmax = static_cast<float>(reach_hint);
   // supertile candidate lists of the two-level kernel (stream-ordered caching allocator)
-  void *scratch = nullptr;
-  if (int rc = psh_malloc(&scratch, psh::idw_scratch_bytes(m, n))) return rc;
-  a.scratch = scratch;
-  const hipError_t le = psh::launch_idw(a, c.stream);
-  (void)psh_free(scratch);
-  if (le != hipSuccess) return psh::fail(PSH_EHIP, "idw launch failed: %s", hipGetErrorString(le));
+  psh::Scratch scratch;
+  if (int rc = scratch.alloc(psh::idw_scratch_bytes(m, n))) return rc;
+  a.scratch = scratch.as<void>();
+  PSH_HIP(psh::launch_idw(a, c.stream));
   return PSH_OK;
 }
 
@@ -1044,12 +1042,10 @@ int idw_resident(const float *xy_dev, const float *values_dev, int capacity, con
   a.offset = static_cast<float>(dist_offset);
   a.dmax = 1.f;
   a.dyn = dyn_dev;
-  void *scratch = nullptr;
-  if (int rc = psh_malloc(&scratch, idw_scratch_bytes(m, n))) return rc;
-  a.scratch = scratch;
-  const hipError_t le = launch_idw(a, c.stream);
-  (void)psh_free(scratch);
-  if (le != hipSuccess) return fail(PSH_EHIP, "idw launch failed: %s", hipGetErrorString(le));
+  psh::Scratch scratch;
+  if (int rc = scratch.alloc(idw_scratch_bytes(m, n))) return rc;
+  a.scratch = scratch.as<void>();
+  PSH_HIP(launch_idw(a, c.stream));
   return PSH_OK;
 }
 }  // namespace psh

@@ -157,13 +157,10 @@ extern "C" int psh_lagprob_dev(const void *fields_dev, int fields_f64, int T, in
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(m) * (static_cast<size_t>(n) + 1) * sizeof(uint32_t))) return rc;
-  uint32_t *prefix = static_cast<uint32_t *>(blk);
-  const int rc = fields_f64 ? run_planes(static_cast<const double *>(fields_dev), T, m, n, threshold, scales_host, span_lo_host,
-                                         span_hi_host, prefix, out_dev, c.stream)
-                            : run_planes(static_cast<const float *>(fields_dev), T, m, n, threshold, scales_host, span_lo_host,
-                                         span_hi_host, prefix, out_dev, c.stream);
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(m) * (static_cast<size_t>(n) + 1) * sizeof(uint32_t))) return rc;
+  uint32_t *prefix = blk.as<uint32_t>();
+  return with_real(fields_dev, fields_f64 != 0, [&](auto *fields) {
+    return run_planes(fields, T, m, n, threshold, scales_host, span_lo_host, span_hi_host, prefix, out_dev, c.stream);
+  });
 }

@@ -2069,12 +2069,10 @@ int psh_lk_prepare_f64_dev(const double *frame_dev, int m, int n, int size_openi
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   if (m <= 0 || n <= 0) return fail(PSH_EINVAL, "lk_prepare: invalid shape (%d,%d)", m, n);
-  void *blk = nullptr;  // [clean64 | partials | dstats]
-  if (int rc = psh_malloc(&blk, psh::lk_prepare_ws_bytes(m, n, true))) return rc;
-  const int rc = psh::lk_prepare_on(c.stream, blk, frame_dev, true, m, n, size_opening, buffer_mask, clean_dev,
-                                    track_u8_dev, feature_u8_dev, stats_dev);
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;  // [clean64 | partials | dstats]
+  if (int rc = blk.alloc(psh::lk_prepare_ws_bytes(m, n, true))) return rc;
+  return psh::lk_prepare_on(c.stream, blk.as<void>(), frame_dev, true, m, n, size_opening, buffer_mask, clean_dev,
+                            track_u8_dev, feature_u8_dev, stats_dev);
 }
 
 // ---- row bands (multi-GPU tiling of the image passes, BASELINE config 5) --------------------
@@ -2385,14 +2383,14 @@ int lk_corners_resident(const unsigned char *feature_u8_dev, const float *clean_
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const CornerWs w(m, n, block_size);
-  void *ws = nullptr;
-  if (int rc = psh_malloc(&ws, w.bytes)) return rc;  // stream-ordered caching allocator
+  Scratch ws;  // freed stream-ordered: the kernels below are queued in front of any reuse
+  if (int rc = ws.alloc(w.bytes)) return rc;
   const int *count_dev = nullptr;
   int count_bias = 0;
-  int rc = corner_candidates(w, ws, feature_u8_dev, clean_dev, stats_dev, m, n, block_size, buffer_mask, quality_level,
+  int rc = corner_candidates(w, ws.as<void>(), feature_u8_dev, clean_dev, stats_dev, m, n, block_size, buffer_mask, quality_level,
                              slots_cleared, &count_dev, &count_bias);
   if (rc == PSH_OK) {
-    char *base = static_cast<char *>(ws);
+    char *base = ws.as<char>();
     const hipError_t e = launch_corner_order(
         reinterpret_cast<const CornerKey *>(base + w.off_raw), count_dev, w.cap,
         stats_dev + kEigMax, static_cast<float>(quality_level), n, min_distance, max_corners, base + w.off_ord,
@@ -2406,7 +2404,6 @@ int lk_corners_resident(const unsigned char *feature_u8_dev, const float *clean_
         rc = fail(PSH_EHIP, "corner_order statistics copy failed");
     }
   }
-  (void)psh_free(ws);  // the kernels above are queued in front of any reuse
   return rc;
 }
 }  // namespace psh
@@ -2429,34 +2426,27 @@ int psh_lk_corners_launch_dev(const unsigned char *feature_u8_dev, const float *
   if (int rc = psh::persistent_pinned(&job.pinned, pin_need)) return rc;
   char *pin = static_cast<char *>(job.pinned);
   const CornerWs w(m, n, block_size);
-  void *ws = nullptr;
+  psh::Scratch ws;  // host_ordered: handed to the job once everything is queued; else freed behind the copy
   if (host_ordered) {
-    if (int rc = psh_malloc(&ws, w.bytes)) return rc;
-    if (int rc = corner_candidates(w, ws, feature_u8_dev, clean_dev, stats_dev, m, n, block_size, buffer_mask,
-                                   quality_level)) {
-      (void)psh_free(ws);
+    if (int rc = ws.alloc(w.bytes)) return rc;
+    if (int rc = corner_candidates(w, ws.as<void>(), feature_u8_dev, clean_dev, stats_dev, m, n, block_size, buffer_mask,
+                                   quality_level))
       return rc;
-    }
-    PSH_HIP(hipMemcpyAsync(pin, static_cast<char *>(ws) + w.off_cnt, sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    job.raw_dev = reinterpret_cast<psh::CornerKey *>(static_cast<char *>(ws) + w.off_raw);
+    PSH_HIP(hipMemcpyAsync(pin, ws.at<char>(w.off_cnt), sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    job.raw_dev = ws.at<psh::CornerKey>(w.off_raw);
   } else {
     // accepted corners and their count in device memory, then one copy of both behind the kernels
     const size_t pts_bytes = static_cast<size_t>(max_corners) * sizeof(float2);
-    if (int rc = psh_malloc(&ws, kPinnedHeader + pts_bytes)) return rc;
-    char *blk = static_cast<char *>(ws);
-    const int rc = psh::lk_corners_resident(feature_u8_dev, clean_dev, stats_dev, m, n, block_size, buffer_mask,
-                                            quality_level, min_distance, max_corners,
-                                            reinterpret_cast<float *>(blk + kPinnedHeader), reinterpret_cast<int *>(blk));
-    if (rc != PSH_OK) {
-      (void)psh_free(ws);
+    if (int rc = ws.alloc(kPinnedHeader + pts_bytes)) return rc;
+    if (int rc = psh::lk_corners_resident(feature_u8_dev, clean_dev, stats_dev, m, n, block_size, buffer_mask,
+                                          quality_level, min_distance, max_corners, ws.at<float>(kPinnedHeader),
+                                          ws.as<int>()))
       return rc;
-    }
-    PSH_HIP(hipMemcpyAsync(pin, blk, kPinnedHeader + pts_bytes, hipMemcpyDeviceToHost, c.stream));
-    (void)psh_free(ws);  // stream-ordered: the copy above is queued first
-    ws = nullptr;
+    PSH_HIP(hipMemcpyAsync(pin, ws.as<char>(), kPinnedHeader + pts_bytes, hipMemcpyDeviceToHost, c.stream));
+    ws.reset();  // stream-ordered: the copy above is queued first
   }
   PSH_HIP(hipEventRecord(job.ready, c.stream));
-  job.ws = ws;
+  job.ws = ws.release();
   job.active = true;
   job.host_ordered = host_ordered;
   ++g_corner_count;
@@ -2480,12 +2470,7 @@ int psh_lk_corners_finish(float *points_host, int *count_host) {
   --g_corner_count;
   job.active = false;
   // whatever happens below, the request's device block goes back to the allocator
-  struct Release {
-    void *p;
-    ~Release() {
-      if (p) (void)psh_free(p);
-    }
-  } release{job.ws};
+  const psh::Scratch ws(job.ws);
   job.ws = nullptr;
   PSH_HIP(hipEventSynchronize(job.ready));
   const char *pin = static_cast<const char *>(job.pinned);
@@ -2612,11 +2597,9 @@ int lk_pyramids_on_side(hipStream_t side, void *block, size_t block_bytes, const
                         void **handle_out) {
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
+  Scratch own(block);  // (psh_free of a block of the allocator succeeds and leaves psh_last_error() alone)
   const int rc = lk_pyramids_on(side, prev_u8_dev, next_u8_dev, m, n, win_w, win_h, max_level, handle_out, block, block_bytes);
-  if (rc != PSH_OK && block) {
-    // (psh_free of a block of the allocator succeeds and leaves psh_last_error() alone)
-    (void)psh_free(block);
-  }
+  if (rc == PSH_OK) (void)own.release();
   return rc;
 }
 size_t lk_pyramids_bytes(int m, int n, int win_w, int win_h, int max_level) {
@@ -2867,28 +2850,23 @@ int psh_lk_track_pyr_dev(void *handle, const float *points_host, int npts, int m
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const size_t pts_bytes = (static_cast<size_t>(npts) * sizeof(float2) + 255) & ~static_cast<size_t>(255);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 2 * pts_bytes + static_cast<size_t>(npts))) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(2 * pts_bytes + static_cast<size_t>(npts))) return rc;
+  char *base = blk.as<char>();
   float2 *d_pts = reinterpret_cast<float2 *>(base);
   float2 *d_next = reinterpret_cast<float2 *>(base + pts_bytes);
   unsigned char *d_st = reinterpret_cast<unsigned char *>(base + 2 * pts_bytes);
   const float eps = static_cast<float>(epsilon);
-  auto run = [&]() -> int {
-    PSH_HIP(hipMemcpyAsync(d_pts, points_host, static_cast<size_t>(npts) * sizeof(float2),
-                           hipMemcpyHostToDevice, c.stream));
-    launch_lk_track(npts, nullptr, c.stream, ps->pyr, d_pts, ps->win_w, ps->win_h, max_count, eps * eps,
-                    static_cast<float>(min_eig_threshold), d_next, d_st);
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(next_points_host, d_next, static_cast<size_t>(npts) * sizeof(float2),
-                           hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipMemcpyAsync(status_host, d_st, static_cast<size_t>(npts), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  PSH_HIP(hipMemcpyAsync(d_pts, points_host, static_cast<size_t>(npts) * sizeof(float2),
+                         hipMemcpyHostToDevice, c.stream));
+  launch_lk_track(npts, nullptr, c.stream, ps->pyr, d_pts, ps->win_w, ps->win_h, max_count, eps * eps,
+                  static_cast<float>(min_eig_threshold), d_next, d_st);
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(next_points_host, d_next, static_cast<size_t>(npts) * sizeof(float2),
+                         hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipMemcpyAsync(status_host, d_st, static_cast<size_t>(npts), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  return PSH_OK;
 }
 
 int psh_lk_track_dev(const unsigned char *prev_u8_dev, const unsigned char *next_u8_dev, int m,
@@ -2922,44 +2900,39 @@ int lk_track_pool(void *pyramid_handle, const float *points_host, const float *p
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const size_t pts_bytes = (static_cast<size_t>(npts) * sizeof(float2) + 255) & ~static_cast<size_t>(255);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 2 * pts_bytes + static_cast<size_t>(npts))) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(2 * pts_bytes + static_cast<size_t>(npts))) return rc;
+  char *base = blk.as<char>();
   float2 *d_pts = reinterpret_cast<float2 *>(base);
   float2 *d_next = reinterpret_cast<float2 *>(base + pts_bytes);
   unsigned char *d_st = reinterpret_cast<unsigned char *>(base + 2 * pts_bytes);
   const float eps = static_cast<float>(epsilon);
-  auto run = [&]() -> int {
-    const float2 *pts = reinterpret_cast<const float2 *>(points_dev);
-    if (points_host) {
-      // pinned staging slot per call (ring): the copy is asynchronous and the caller's buffer may
-      // be reused at once
-      static void *ring = nullptr;
-      static size_t ring_slot = 0;
-      constexpr size_t kSlots = 8, kSlotBytes = 1 << 16;
-      if (static_cast<size_t>(npts) * sizeof(float2) > kSlotBytes)
-        return fail(PSH_EUNSUPPORTED, "lk_track_pool: more than %zu points", kSlotBytes / sizeof(float2));
-      if (int rc = persistent_pinned(&ring, kSlots * kSlotBytes)) return rc;
-      if (ring_slot == kSlots) {
-        PSH_HIP(hipStreamSynchronize(c.stream));
-        ring_slot = 0;
-      }
-      char *slot = static_cast<char *>(ring) + (ring_slot++) * kSlotBytes;
-      std::memcpy(slot, points_host, static_cast<size_t>(npts) * sizeof(float2));
-      PSH_HIP(hipMemcpyAsync(d_pts, slot, static_cast<size_t>(npts) * sizeof(float2), hipMemcpyHostToDevice, c.stream));
-      pts = d_pts;
+  const float2 *pts = reinterpret_cast<const float2 *>(points_dev);
+  if (points_host) {
+    // pinned staging slot per call (ring): the copy is asynchronous and the caller's buffer may
+    // be reused at once
+    static void *ring = nullptr;
+    static size_t ring_slot = 0;
+    constexpr size_t kSlots = 8, kSlotBytes = 1 << 16;
+    if (static_cast<size_t>(npts) * sizeof(float2) > kSlotBytes)
+      return fail(PSH_EUNSUPPORTED, "lk_track_pool: more than %zu points", kSlotBytes / sizeof(float2));
+    if (int rc = persistent_pinned(&ring, kSlots * kSlotBytes)) return rc;
+    if (ring_slot == kSlots) {
+      PSH_HIP(hipStreamSynchronize(c.stream));
+      ring_slot = 0;
     }
-    launch_lk_track(npts, npts_dev, c.stream, ps->pyr, pts, ps->win_w, ps->win_h, max_count, eps * eps,
-                    static_cast<float>(min_eig_threshold), d_next, d_st);
-    hipLaunchKernelGGL(lk_pool_append, dim3(1), dim3(256), 0, c.stream, pts, d_next, d_st, npts, npts_dev,
-                       reinterpret_cast<double2 *>(pool_xy_dev), reinterpret_cast<double2 *>(pool_uv_dev),
-                       pool_count_dev, pool_capacity);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+    char *slot = static_cast<char *>(ring) + (ring_slot++) * kSlotBytes;
+    std::memcpy(slot, points_host, static_cast<size_t>(npts) * sizeof(float2));
+    PSH_HIP(hipMemcpyAsync(d_pts, slot, static_cast<size_t>(npts) * sizeof(float2), hipMemcpyHostToDevice, c.stream));
+    pts = d_pts;
+  }
+  launch_lk_track(npts, npts_dev, c.stream, ps->pyr, pts, ps->win_w, ps->win_h, max_count, eps * eps,
+                  static_cast<float>(min_eig_threshold), d_next, d_st);
+  hipLaunchKernelGGL(lk_pool_append, dim3(1), dim3(256), 0, c.stream, pts, d_next, d_st, npts, npts_dev,
+                     reinterpret_cast<double2 *>(pool_xy_dev), reinterpret_cast<double2 *>(pool_uv_dev),
+                     pool_count_dev, pool_capacity);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 }  // namespace psh

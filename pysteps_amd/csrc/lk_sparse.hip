@@ -1030,41 +1030,35 @@ extern "C" int psh_lk_order_host(const unsigned long long *keys_host, int count,
   PSH_HIP(hipSetDevice(c.device));
   const size_t key_bytes = (static_cast<size_t>(count) * sizeof(unsigned long long) + 255) & ~static_cast<size_t>(255);
   const size_t pts_bytes = static_cast<size_t>(max_corners) * 2 * sizeof(float);
-  void *blk = nullptr;
+  psh::Scratch blk;
   const size_t ws_bytes = (psh::corner_order_ws_bytes() + 255) & ~static_cast<size_t>(255);
-  if (int rc = psh_malloc(&blk, key_bytes + 256 + pts_bytes + 256 + ws_bytes)) return rc;
-  char *base = static_cast<char *>(blk);
+  if (int rc = blk.alloc(key_bytes + 256 + pts_bytes + 256 + ws_bytes)) return rc;
+  char *base = blk.as<char>();
   unsigned long long *d_keys = reinterpret_cast<unsigned long long *>(base);
   int *d_hdr = reinterpret_cast<int *>(base + key_bytes);  // [count | accepted | response max (float)]
   float *d_pts = reinterpret_cast<float *>(base + key_bytes + 256);
   void *d_ws = base + ((key_bytes + 256 + pts_bytes + 255) & ~static_cast<size_t>(255));
-  int rc = PSH_OK;
-  auto run = [&]() -> int {
-    struct {
-      int count, accepted;
-      float top;
-    } hdr = {count, 0, response_max};
-    if (count > 0) PSH_HIP(hipMemcpyAsync(d_keys, keys_host, static_cast<size_t>(count) * 8, hipMemcpyHostToDevice, c.stream));
-    PSH_HIP(hipMemcpyAsync(d_hdr, &hdr, sizeof(hdr), hipMemcpyHostToDevice, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));  // hdr lives on this stack frame
-    PSH_HIP(psh::launch_corner_order(d_keys, d_hdr, count, reinterpret_cast<const float *>(d_hdr + 2),
-                                     static_cast<float>(quality_level), n, min_distance, max_corners, d_ws, d_pts,
-                                     d_hdr + 1, c.stream, nullptr, nullptr, false));
-    int accepted = 0;
-    PSH_HIP(hipMemcpyAsync(&accepted, d_hdr + 1, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  struct {
+    int count, accepted;
+    float top;
+  } hdr = {count, 0, response_max};
+  if (count > 0) PSH_HIP(hipMemcpyAsync(d_keys, keys_host, static_cast<size_t>(count) * 8, hipMemcpyHostToDevice, c.stream));
+  PSH_HIP(hipMemcpyAsync(d_hdr, &hdr, sizeof(hdr), hipMemcpyHostToDevice, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));  // hdr lives on this stack frame
+  PSH_HIP(psh::launch_corner_order(d_keys, d_hdr, count, reinterpret_cast<const float *>(d_hdr + 2),
+                                   static_cast<float>(quality_level), n, min_distance, max_corners, d_ws, d_pts,
+                                   d_hdr + 1, c.stream, nullptr, nullptr, false));
+  int accepted = 0;
+  PSH_HIP(hipMemcpyAsync(&accepted, d_hdr + 1, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  accepted = accepted < 0 ? 0 : accepted > max_corners ? max_corners : accepted;
+  if (accepted > 0) {
+    PSH_HIP(hipMemcpyAsync(points_host, d_pts, static_cast<size_t>(accepted) * 2 * sizeof(float), hipMemcpyDeviceToHost,
+                           c.stream));
     PSH_HIP(hipStreamSynchronize(c.stream));
-    accepted = accepted < 0 ? 0 : accepted > max_corners ? max_corners : accepted;
-    if (accepted > 0) {
-      PSH_HIP(hipMemcpyAsync(points_host, d_pts, static_cast<size_t>(accepted) * 2 * sizeof(float), hipMemcpyDeviceToHost,
-                             c.stream));
-      PSH_HIP(hipStreamSynchronize(c.stream));
-    }
-    *count_host = accepted;
-    return PSH_OK;
-  };
-  rc = run();
-  (void)psh_free(blk);
-  return rc;
+  }
+  *count_host = accepted;
+  return PSH_OK;
 }
 
 extern "C" int psh_vectors_finish_host(const double *xy, const double *values, const unsigned char *outlier_flags,
@@ -1082,39 +1076,34 @@ extern "C" int psh_vectors_finish_host(const double *xy, const double *values, c
   const size_t cap = static_cast<size_t>(count > 0 ? count : 1);
   const size_t vec = cap * 16, off_uv = vec, off_fl = 2 * vec, off_cnt = (off_fl + cap + 255) & ~static_cast<size_t>(255);
   const size_t off_oxy = off_cnt + 256, off_ouv = off_oxy + cap * 8, off_dyn = off_ouv + cap * 8;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, off_dyn + sizeof(psh::IdwDyn))) return rc;
-  char *base = static_cast<char *>(blk);
-  auto run = [&]() -> int {
-    if (count > 0) {
-      PSH_HIP(hipMemcpyAsync(base, xy, vec, hipMemcpyHostToDevice, c.stream));
-      PSH_HIP(hipMemcpyAsync(base + off_uv, values, vec, hipMemcpyHostToDevice, c.stream));
-      PSH_HIP(hipMemcpyAsync(base + off_fl, outlier_flags, cap, hipMemcpyHostToDevice, c.stream));
-    }
-    PSH_HIP(hipMemcpyAsync(base + off_cnt, &count, sizeof(int), hipMemcpyHostToDevice, c.stream));
+  psh::Scratch blk;
+  if (int rc = blk.alloc(off_dyn + sizeof(psh::IdwDyn))) return rc;
+  char *base = blk.as<char>();
+  if (count > 0) {
+    PSH_HIP(hipMemcpyAsync(base, xy, vec, hipMemcpyHostToDevice, c.stream));
+    PSH_HIP(hipMemcpyAsync(base + off_uv, values, vec, hipMemcpyHostToDevice, c.stream));
+    PSH_HIP(hipMemcpyAsync(base + off_fl, outlier_flags, cap, hipMemcpyHostToDevice, c.stream));
+  }
+  PSH_HIP(hipMemcpyAsync(base + off_cnt, &count, sizeof(int), hipMemcpyHostToDevice, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  PSH_HIP(psh::launch_vectors_finish(reinterpret_cast<const double *>(base), reinterpret_cast<const double *>(base + off_uv),
+                                     reinterpret_cast<const unsigned char *>(base + off_fl),
+                                     reinterpret_cast<const int *>(base + off_cnt), static_cast<int>(cap), decl_scale, m, n,
+                                     reinterpret_cast<float *>(base + off_oxy), reinterpret_cast<float *>(base + off_ouv),
+                                     reinterpret_cast<psh::IdwDyn *>(base + off_dyn), c.stream));
+  psh::IdwDyn d;
+  PSH_HIP(hipMemcpyAsync(&d, base + off_dyn, sizeof(d), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  const int L = d.L < 0 ? 0 : d.L > count ? count : d.L;
+  if (L > 0) {
+    PSH_HIP(hipMemcpyAsync(out_xy, base + off_oxy, static_cast<size_t>(L) * 8, hipMemcpyDeviceToHost, c.stream));
+    PSH_HIP(hipMemcpyAsync(out_values, base + off_ouv, static_cast<size_t>(L) * 8, hipMemcpyDeviceToHost, c.stream));
     PSH_HIP(hipStreamSynchronize(c.stream));
-    PSH_HIP(psh::launch_vectors_finish(reinterpret_cast<const double *>(base), reinterpret_cast<const double *>(base + off_uv),
-                                       reinterpret_cast<const unsigned char *>(base + off_fl),
-                                       reinterpret_cast<const int *>(base + off_cnt), static_cast<int>(cap), decl_scale, m, n,
-                                       reinterpret_cast<float *>(base + off_oxy), reinterpret_cast<float *>(base + off_ouv),
-                                       reinterpret_cast<psh::IdwDyn *>(base + off_dyn), c.stream));
-    psh::IdwDyn d;
-    PSH_HIP(hipMemcpyAsync(&d, base + off_dyn, sizeof(d), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    const int L = d.L < 0 ? 0 : d.L > count ? count : d.L;
-    if (L > 0) {
-      PSH_HIP(hipMemcpyAsync(out_xy, base + off_oxy, static_cast<size_t>(L) * 8, hipMemcpyDeviceToHost, c.stream));
-      PSH_HIP(hipMemcpyAsync(out_values, base + off_ouv, static_cast<size_t>(L) * 8, hipMemcpyDeviceToHost, c.stream));
-      PSH_HIP(hipStreamSynchronize(c.stream));
-    }
-    *out_count = L;
-    *out_mode = d.mode;
-    out_const[0] = d.cu;
-    out_const[1] = d.cv;
-    *out_reach = d.reach;
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  }
+  *out_count = L;
+  *out_mode = d.mode;
+  out_const[0] = d.cu;
+  out_const[1] = d.cv;
+  *out_reach = d.reach;
+  return PSH_OK;
 }

@@ -343,30 +343,25 @@ extern "C" int psh_dilated_mask_dev(const unsigned char *mask_dev, int m, int n,
   }
   const size_t total = static_cast<size_t>(m) * n;
   auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 256 + 2 * up(total))) return rc;  // [any | mask0 | g]
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(256 + 2 * up(total))) return rc;  // [any | mask0 | g]
+  char *base = blk.as<char>();
   int *any = reinterpret_cast<int *>(base);
   unsigned char *mask0 = reinterpret_cast<unsigned char *>(base + 256);
   unsigned char *g = mask0 + up(total);
-  auto run = [&]() -> int {
-    hipStream_t s = c.stream;
-    if (ntaps)
-      PSH_HIP(hipMemcpyAsync(const_cast<float *>(slot_dev), slot_host, static_cast<size_t>(ntaps) * sizeof(short2),
-                             hipMemcpyHostToDevice, s));
-    PSH_HIP(hipMemsetAsync(any, 0, sizeof(int), s));
-    const size_t groups = static_cast<size_t>(m) * ((n + 3) / 4);  // four pixels of a row per thread
-    const int grid = static_cast<int>(std::min<size_t>(kGrid, (groups + kThreads - 1) / kThreads));
-    hipLaunchKernelGGL(mask_dilate, dim3(grid), dim3(kThreads), 0, s, mask_dev, m, n,
-                       reinterpret_cast<const short2 *>(slot_dev), ntaps, reach, mask0, any);
-    hipLaunchKernelGGL(mask_column_distance, dim3(grid), dim3(kThreads), 0, s, mask0, m, n, r, g);
-    hipLaunchKernelGGL(mask_rim, dim3(grid), dim3(kThreads), 0, s, g, m, n, r, any, out_dev);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  hipStream_t s = c.stream;
+  if (ntaps)
+    PSH_HIP(hipMemcpyAsync(const_cast<float *>(slot_dev), slot_host, static_cast<size_t>(ntaps) * sizeof(short2),
+                           hipMemcpyHostToDevice, s));
+  PSH_HIP(hipMemsetAsync(any, 0, sizeof(int), s));
+  const size_t groups = static_cast<size_t>(m) * ((n + 3) / 4);  // four pixels of a row per thread
+  const int grid = static_cast<int>(std::min<size_t>(kGrid, (groups + kThreads - 1) / kThreads));
+  hipLaunchKernelGGL(mask_dilate, dim3(grid), dim3(kThreads), 0, s, mask_dev, m, n,
+                     reinterpret_cast<const short2 *>(slot_dev), ntaps, reach, mask0, any);
+  hipLaunchKernelGGL(mask_column_distance, dim3(grid), dim3(kThreads), 0, s, mask0, m, n, r, g);
+  hipLaunchKernelGGL(mask_rim, dim3(grid), dim3(kThreads), 0, s, g, m, n, r, any, out_dev);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 // `field >= threshold` (steps.py:1211) and compute_dilated_mask(., kr, r) (nowcasts/utils.py:69-101) of a float64 field in
@@ -413,29 +408,24 @@ extern "C" int psh_steps_incremental_mask_dev(const double *field_dev, int m, in
   c.mask_generation = c.mask_generation == 0x7fffffff ? 1 : c.mask_generation + 1;
   int *any = c.mask_any;
   const int generation = c.mask_generation;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, bit_bytes)) return rc;
-  unsigned long long *bits = static_cast<unsigned long long *>(blk);
-  auto run = [&]() -> int {
-    hipStream_t s = c.stream;
-    const size_t words = static_cast<size_t>(m) * words_per_row;
-    const int wgrid = static_cast<int>(std::min<size_t>((words + 15) / 16, static_cast<size_t>(c.cu_count) * 16));
-    hipLaunchKernelGGL(wet_bits, dim3(std::max(wgrid, 1)), dim3(256), 0, s, field_dev, m, n, threshold, bits, words_per_row, any,
-                       generation);
-    const int side = 64 - 2 * halo;
-    const int tiles_x = (n + side - 1) / side, tiles_y = (m + side - 1) / side, n_tiles = tiles_x * tiles_y;
-    const dim3 grid((n_tiles + kBitsWaves - 1) / kBitsWaves), block(64 * kBitsWaves);
-    if (r + 1 < 16) {
-      hipLaunchKernelGGL(mask_from_bits<4>, grid, block, 0, s, bits, words_per_row, m, n, taps, ntaps, halo, r, any, generation, out_dev,
-                         tiles_x, n_tiles);
-    } else {
-      hipLaunchKernelGGL(mask_from_bits<8>, grid, block, 0, s, bits, words_per_row, m, n, taps, ntaps, halo, r, any, generation, out_dev,
-                         tiles_x, n_tiles);
-    }
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(bit_bytes)) return rc;
+  unsigned long long *bits = blk.as<unsigned long long>();
+  hipStream_t s = c.stream;
+  const size_t words = static_cast<size_t>(m) * words_per_row;
+  const int wgrid = static_cast<int>(std::min<size_t>((words + 15) / 16, static_cast<size_t>(c.cu_count) * 16));
+  hipLaunchKernelGGL(wet_bits, dim3(std::max(wgrid, 1)), dim3(256), 0, s, field_dev, m, n, threshold, bits, words_per_row, any,
+                     generation);
+  const int side = 64 - 2 * halo;
+  const int tiles_x = (n + side - 1) / side, tiles_y = (m + side - 1) / side, n_tiles = tiles_x * tiles_y;
+  const dim3 grid((n_tiles + kBitsWaves - 1) / kBitsWaves), block(64 * kBitsWaves);
+  if (r + 1 < 16) {
+    hipLaunchKernelGGL(mask_from_bits<4>, grid, block, 0, s, bits, words_per_row, m, n, taps, ntaps, halo, r, any, generation, out_dev,
+                       tiles_x, n_tiles);
+  } else {
+    hipLaunchKernelGGL(mask_from_bits<8>, grid, block, 0, s, bits, words_per_row, m, n, taps, ntaps, halo, r, any, generation, out_dev,
+                       tiles_x, n_tiles);
+  }
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }

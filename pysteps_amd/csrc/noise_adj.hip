@@ -259,21 +259,16 @@ extern "C" int psh_noise_adj_prepare_dev(double *fields_dev, int nbatch, size_t 
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *stats = nullptr;
-  if (int rc = psh_malloc(&stats, static_cast<size_t>(nbatch) * sizeof(double2))) return rc;
-  auto run = [&]() -> int {
-    // np.std(N) of every realisation: the moments kernels the noise filter standardises with, per plane
-    if (int rc = psh::moments(fields_dev, nbatch, plane, static_cast<double2 *>(stats), c.stream)) return rc;
-    if (stats_out_dev)
-      PSH_HIP(hipMemcpyAsync(stats_out_dev, stats, static_cast<size_t>(nbatch) * sizeof(double2), hipMemcpyDeviceToDevice, c.stream));
-    hipLaunchKernelGGL(psh::prepare, dim3(std::min(psh::sweep_blocks(plane), 2048u), nbatch), dim3(psh::kThreads), 0, c.stream,
-                       fields_dev, plane, mask_dev, static_cast<const double2 *>(stats), sigma, mu, thr2);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(stats);  // stream-ordered
-  return rc;
+  psh::Scratch stats;
+  if (int rc = stats.alloc(static_cast<size_t>(nbatch) * sizeof(double2))) return rc;
+  // np.std(N) of every realisation: the moments kernels the noise filter standardises with, per plane
+  if (int rc = psh::moments(fields_dev, nbatch, plane, stats.as<double2>(), c.stream)) return rc;
+  if (stats_out_dev)
+    PSH_HIP(hipMemcpyAsync(stats_out_dev, stats.as<void>(), static_cast<size_t>(nbatch) * sizeof(double2), hipMemcpyDeviceToDevice, c.stream));
+  hipLaunchKernelGGL(psh::prepare, dim3(std::min(psh::sweep_blocks(plane), 2048u), nbatch), dim3(psh::kThreads), 0, c.stream,
+                     fields_dev, plane, mask_dev, stats.as<const double2>(), sigma, mu, thr2);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 extern "C" int psh_mask_count_dev(const unsigned char *mask_dev, size_t plane, unsigned long long *count_dev) {
@@ -298,9 +293,9 @@ extern "C" int psh_masked_moments_dev(const double *planes_dev, int nplanes, siz
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *partial = nullptr;
-  if (int rc = psh_malloc(&partial, static_cast<size_t>(nplanes) * psh::kPartBlocks * sizeof(psh::Part))) return rc;
-  psh::Part *part = static_cast<psh::Part *>(partial);
+  psh::Scratch partial;
+  if (int rc = partial.alloc(static_cast<size_t>(nplanes) * psh::kPartBlocks * sizeof(psh::Part))) return rc;
+  psh::Part *part = partial.as<psh::Part>();
   if (planes_per_block == 4)
     hipLaunchKernelGGL(psh::masked_partial<4>, dim3(psh::kPartBlocks, (nplanes + 3) / 4), dim3(psh::kThreads), 0, c.stream,
                        planes_dev, nplanes, plane, mask_dev, part);
@@ -309,9 +304,7 @@ extern "C" int psh_masked_moments_dev(const double *planes_dev, int nplanes, siz
                        nplanes, plane, mask_dev, part);
   hipLaunchKernelGGL(psh::masked_final, dim3(nplanes), dim3(psh::kThreads), 0, c.stream, static_cast<const psh::Part *>(part),
                      psh::kPartBlocks, count_dev, reinterpret_cast<double2 *>(stats_dev));
-  const hipError_t e = hipGetLastError();
-  (void)psh_free(partial);  // stream-ordered
-  PSH_HIP(e);
+  PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
@@ -326,16 +319,14 @@ extern "C" int psh_spectrum_level_moments_dev(const void *spec_dev, int nspec, c
   PSH_HIP(hipSetDevice(c.device));
   const int nc = n / 2 + 1;
   const int grid = std::min(m, 1024);  // rows are dealt to the blocks; a function of the shape alone
-  void *partial = nullptr;
-  if (int rc = psh_malloc(&partial, static_cast<size_t>(nspec) * grid * psh::kMaxLevels * sizeof(double))) return rc;
+  psh::Scratch partial;
+  if (int rc = partial.alloc(static_cast<size_t>(nspec) * grid * psh::kMaxLevels * sizeof(double))) return rc;
   hipLaunchKernelGGL(psh::spectrum_partial, dim3(grid, nspec), dim3(psh::kThreads), 0, c.stream,
                      static_cast<const double2 *>(spec_dev), weights_dev, nlevels, m, nc, (n & 1) == 0 ? 1 : 0,
-                     static_cast<double *>(partial));
+                     partial.as<double>());
   hipLaunchKernelGGL(psh::spectrum_final, dim3(nlevels, nspec), dim3(psh::kThreads), 0, c.stream,
-                     static_cast<const double *>(partial), grid, static_cast<const double2 *>(spec_dev), weights_dev,
+                     partial.as<const double>(), grid, static_cast<const double2 *>(spec_dev), weights_dev,
                      static_cast<size_t>(m) * nc, static_cast<double>(m) * n, reinterpret_cast<double2 *>(stats_dev));
-  const hipError_t e = hipGetLastError();
-  (void)psh_free(partial);  // stream-ordered
-  PSH_HIP(e);
+  PSH_HIP(hipGetLastError());
   return PSH_OK;
 }

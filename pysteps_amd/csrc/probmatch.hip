@@ -945,9 +945,9 @@ static int probmatch_run(const double *initial_dev, const double *target_dev, si
   const size_t off_rec_b = up(off_rec_a + (make ? 0 : count * sizeof(PmRec)));
   const size_t total = off_rec_b + (make ? 0 : count * sizeof(PmRec));
   static_assert(sizeof(PmHeader) <= 256, "header block");
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, total)) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(total)) return rc;
+  char *base = blk.as<char>();
   PmHeader *h = reinterpret_cast<PmHeader *>(base);
   PmPartial *part = reinterpret_cast<PmPartial *>(base + off_part);
   unsigned *cnt = reinterpret_cast<unsigned *>(base + off_count);
@@ -965,69 +965,59 @@ static int probmatch_run(const double *initial_dev, const double *target_dev, si
   PmRec *rec_a = reinterpret_cast<PmRec *>(base + off_rec_a);
   PmRec *rec_b = reinterpret_cast<PmRec *>(base + off_rec_b);
 
-  int status = -1;
-  auto run = [&]() -> int {
-    // every workgroup of the streaming kernels reads at least kLoads x kThreads values
-    const int grid = static_cast<int>(
-        std::min<size_t>(kGrid, (count + kLoads * kThreads - 1) / (static_cast<size_t>(kLoads) * kThreads)));
-    const int grid_large = 1024;
-    const int halves = plan ? 1 : 2;
-    hipStream_t s = c.stream;
-    if (!plan) PSH_HIP(hipMemsetAsync(cnt + kBins, 0, table_bytes / 2, s));  // the target's bucket counts
-    // (the header is reset by pm_prepare; nothing before it reads one)
-    int nparts = grid;
-    if (mask) {  // the member loop's precipitation mask in place + the statistics of what it leaves, one sweep
-      nparts = kGrid;
-      hipLaunchKernelGGL(pm_mask_stats, dim3(nparts), dim3(kThreads), 0, s, const_cast<double *>(initial_dev), count, mask->grey,
-                         mask->keep, mask->min_key, part);
-    } else {
-      hipLaunchKernelGGL(pm_stats, dim3(grid, halves), dim3(kThreads), 0, s, make ? target_dev : initial_dev, target_dev, count,
-                         part);
-    }
-    hipLaunchKernelGGL(pm_prepare, dim3(1), dim3(kThreads), 0, s, h, count, part, nparts, plan ? 0 : (make ? 1 : -1),
-                       plan ? plan->header() : static_cast<const PmHeader *>(nullptr));
-    if (!plan) {  // target: bucket counts, bucket starts, sorted wet values
-      hipLaunchKernelGGL(pm_hist_target, dim3(grid), dim3(kThreads), 0, s, target_dev, count, h, cnt + kBins);
-      hipLaunchKernelGGL(pm_bin_sums, dim3(kScanBlocks, 1), dim3(kThreads), 0, s, cnt, sums, 1);
-      hipLaunchKernelGGL(pm_scan_sums, dim3(1), dim3(kScanBlocks), 0, s, sums, offs, h, 1);
-      hipLaunchKernelGGL(pm_bin_starts, dim3(kScanBlocks, 1), dim3(kThreads), 0, s, cnt, offs, start, cursor, large,
-                         large_cap, h, 1);
-      hipLaunchKernelGGL(pm_scatter_target, dim3(grid), dim3(kThreads), 0, s, target_dev, count, h, cursor + kBins, sval);
-      hipLaunchKernelGGL(pm_rank_small, dim3(grid), dim3(kThreads), 0, s, h, cnt, start, sval, tw);
-      hipLaunchKernelGGL(pm_rank_large, dim3(grid_large), dim3(kThreads), 0, s, h, cnt, start, large, large_cap, sval, tw);
-    }
-    if (make) {  // keep the header and the sorted values
-      PSH_HIP(hipMemcpyAsync(make->blk, h, sizeof(PmHeader), hipMemcpyDeviceToDevice, s));
-      PSH_HIP(hipMemcpyAsync(static_cast<char *>(make->blk) + 256, tw, count * sizeof(double), hipMemcpyDeviceToDevice, s));
-      PSH_HIP(hipGetLastError());
-      status = kStOk;  // the verdict on the target travels in the plan
-      return PSH_OK;
-    }
-    // initial: two partition passes (LDS atomics only), ranks inside the buckets -> output
-    hipLaunchKernelGGL(pm2_count, dim3(nblk), dim3(kThreads), 0, s, initial_dev, count, h, H, nblk);
-    hipLaunchKernelGGL(pm2_sums, dim3(nsums), dim3(kThreads), 0, s, H, nent, hsums);
-    hipLaunchKernelGGL(pm2_offsets, dim3(nsums), dim3(kThreads), 0, s, H, nent, hsums, nsums, h, count, tw);
-    hipLaunchKernelGGL(pm2_scatter, dim3(nblk), dim3(kThreads), 0, s, initial_dev, count, h, H, nblk, rec_a, out_dev);
-    hipLaunchKernelGGL(pm2_refine, dim3(kCoarse), dim3(kRefineThreads), 0, s, h, H, nblk, rec_a, rec_b, large2, large_cap);
-    hipLaunchKernelGGL(pm2_rank, dim3(grid + grid_large), dim3(kThreads), 0, s, h, count, rec_b, tw, out_dev,
-                       static_cast<unsigned>(grid), large2, large_cap);
+  // every workgroup of the streaming kernels reads at least kLoads x kThreads values
+  const int grid = static_cast<int>(
+      std::min<size_t>(kGrid, (count + kLoads * kThreads - 1) / (static_cast<size_t>(kLoads) * kThreads)));
+  const int grid_large = 1024;
+  const int halves = plan ? 1 : 2;
+  hipStream_t s = c.stream;
+  if (!plan) PSH_HIP(hipMemsetAsync(cnt + kBins, 0, table_bytes / 2, s));  // the target's bucket counts
+  // (the header is reset by pm_prepare; nothing before it reads one)
+  int nparts = grid;
+  if (mask) {  // the member loop's precipitation mask in place + the statistics of what it leaves, one sweep
+    nparts = kGrid;
+    hipLaunchKernelGGL(pm_mask_stats, dim3(nparts), dim3(kThreads), 0, s, const_cast<double *>(initial_dev), count, mask->grey,
+                       mask->keep, mask->min_key, part);
+  } else {
+    hipLaunchKernelGGL(pm_stats, dim3(grid, halves), dim3(kThreads), 0, s, make ? target_dev : initial_dev, target_dev, count,
+                       part);
+  }
+  hipLaunchKernelGGL(pm_prepare, dim3(1), dim3(kThreads), 0, s, h, count, part, nparts, plan ? 0 : (make ? 1 : -1),
+                     plan ? plan->header() : static_cast<const PmHeader *>(nullptr));
+  if (!plan) {  // target: bucket counts, bucket starts, sorted wet values
+    hipLaunchKernelGGL(pm_hist_target, dim3(grid), dim3(kThreads), 0, s, target_dev, count, h, cnt + kBins);
+    hipLaunchKernelGGL(pm_bin_sums, dim3(kScanBlocks, 1), dim3(kThreads), 0, s, cnt, sums, 1);
+    hipLaunchKernelGGL(pm_scan_sums, dim3(1), dim3(kScanBlocks), 0, s, sums, offs, h, 1);
+    hipLaunchKernelGGL(pm_bin_starts, dim3(kScanBlocks, 1), dim3(kThreads), 0, s, cnt, offs, start, cursor, large,
+                       large_cap, h, 1);
+    hipLaunchKernelGGL(pm_scatter_target, dim3(grid), dim3(kThreads), 0, s, target_dev, count, h, cursor + kBins, sval);
+    hipLaunchKernelGGL(pm_rank_small, dim3(grid), dim3(kThreads), 0, s, h, cnt, start, sval, tw);
+    hipLaunchKernelGGL(pm_rank_large, dim3(grid_large), dim3(kThreads), 0, s, h, cnt, start, large, large_cap, sval, tw);
+  }
+  if (make) {  // keep the header and the sorted values
+    PSH_HIP(hipMemcpyAsync(make->blk, h, sizeof(PmHeader), hipMemcpyDeviceToDevice, s));
+    PSH_HIP(hipMemcpyAsync(static_cast<char *>(make->blk) + 256, tw, count * sizeof(double), hipMemcpyDeviceToDevice, s));
     PSH_HIP(hipGetLastError());
-    if (status_dev) {  // the caller reads the status later (resident member loop: one wait per time step)
-      PSH_HIP(hipMemcpyAsync(status_dev, &h->status, sizeof(int), hipMemcpyDeviceToDevice, s));
-      status = kStOk;
-      return PSH_OK;
-    }
-    static void *pinned = nullptr;
-    if (int rc = persistent_pinned(&pinned, 64)) return rc;
-    PSH_HIP(hipMemcpyAsync(pinned, &h->status, sizeof(int), hipMemcpyDeviceToHost, s));
-    PSH_HIP(hipStreamSynchronize(s));
-    status = *static_cast<const int *>(pinned);
+    return PSH_OK;  // the verdict on the target travels in the plan
+  }
+  // initial: two partition passes (LDS atomics only), ranks inside the buckets -> output
+  hipLaunchKernelGGL(pm2_count, dim3(nblk), dim3(kThreads), 0, s, initial_dev, count, h, H, nblk);
+  hipLaunchKernelGGL(pm2_sums, dim3(nsums), dim3(kThreads), 0, s, H, nent, hsums);
+  hipLaunchKernelGGL(pm2_offsets, dim3(nsums), dim3(kThreads), 0, s, H, nent, hsums, nsums, h, count, tw);
+  hipLaunchKernelGGL(pm2_scatter, dim3(nblk), dim3(kThreads), 0, s, initial_dev, count, h, H, nblk, rec_a, out_dev);
+  hipLaunchKernelGGL(pm2_refine, dim3(kCoarse), dim3(kRefineThreads), 0, s, h, H, nblk, rec_a, rec_b, large2, large_cap);
+  hipLaunchKernelGGL(pm2_rank, dim3(grid + grid_large), dim3(kThreads), 0, s, h, count, rec_b, tw, out_dev,
+                     static_cast<unsigned>(grid), large2, large_cap);
+  PSH_HIP(hipGetLastError());
+  if (status_dev) {  // the caller reads the status later (resident member loop: one wait per time step)
+    PSH_HIP(hipMemcpyAsync(status_dev, &h->status, sizeof(int), hipMemcpyDeviceToDevice, s));
     return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  if (rc) return rc;
-  return probmatch_status_to_rc(status);
+  }
+  static void *pinned = nullptr;
+  if (int rc = persistent_pinned(&pinned, 64)) return rc;
+  PSH_HIP(hipMemcpyAsync(pinned, &h->status, sizeof(int), hipMemcpyDeviceToHost, s));
+  PSH_HIP(hipStreamSynchronize(s));
+  return probmatch_status_to_rc(*static_cast<const int *>(pinned));
 }
 
 extern "C" int psh_probmatch_dev(const double *initial_dev, const double *target_dev, size_t count, double *out_dev) {

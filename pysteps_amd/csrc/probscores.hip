@@ -364,23 +364,15 @@ extern "C" int psh_crps_sums_dev(const void *fct_dev, int fct_f64, int fct_share
         for (int i = 0; i < 2 * (K + 1); ++i) h[i] = weights_host[i];
       }))
     return rc;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(n_planes) * groups_of(npix, kCrpsMaxGroups) * sizeof(CrpsPartial))) return rc;
-  CrpsPartial *part = static_cast<CrpsPartial *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(n_planes) * groups_of(npix, kCrpsMaxGroups) * sizeof(CrpsPartial))) return rc;
+  CrpsPartial *part = blk.as<CrpsPartial>();
   const size_t stride = fct_shared ? 0 : static_cast<size_t>(K) * npix;
-  int rc;
-  if (fct_f64)
-    rc = obs_f64 ? run_crps(static_cast<const double *>(fct_dev), stride, static_cast<const double *>(obs_dev), n_planes, K, npix,
-                            weights, part, counts_dev, sums_dev, c.stream)
-                 : run_crps(static_cast<const double *>(fct_dev), stride, static_cast<const float *>(obs_dev), n_planes, K, npix,
-                            weights, part, counts_dev, sums_dev, c.stream);
-  else
-    rc = obs_f64 ? run_crps(static_cast<const float *>(fct_dev), stride, static_cast<const double *>(obs_dev), n_planes, K, npix,
-                            weights, part, counts_dev, sums_dev, c.stream)
-                 : run_crps(static_cast<const float *>(fct_dev), stride, static_cast<const float *>(obs_dev), n_planes, K, npix,
-                            weights, part, counts_dev, sums_dev, c.stream);
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  return with_real(fct_dev, fct_f64 != 0, [&](auto *fct) {
+    return with_real(obs_dev, obs_f64 != 0, [&](auto *obs) {
+      return run_crps(fct, stride, obs, n_planes, K, npix, weights, part, counts_dev, sums_dev, c.stream);
+    });
+  });
 }
 
 extern "C" int psh_probbins_dev(const void *prob_dev, int prob_f64, const void *obs_dev, int obs_f64, size_t npix, double x_min,
@@ -409,20 +401,12 @@ extern "C" int psh_probbins_dev(const void *prob_dev, int prob_f64, const void *
         for (int i = 0; i < kBinsLanes; ++i) h[kBinsLanes + 1 + i] = i < n_prob_thrs ? prob_thrs_host[i] : NAN;
       }))
     return rc;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(groups_of(npix, kBinsMaxGroups)) * sizeof(BinsPartial))) return rc;
-  BinsPartial *part = static_cast<BinsPartial *>(blk);
-  int rc;
-  if (prob_f64)
-    rc = obs_f64 ? run_bins(static_cast<const double *>(prob_dev), static_cast<const double *>(obs_dev), npix, x_min, tables, n_bins,
-                            n_prob_thrs, part, bins_dev, sums_dev, roc_dev, c.stream)
-                 : run_bins(static_cast<const double *>(prob_dev), static_cast<const float *>(obs_dev), npix, x_min, tables, n_bins,
-                            n_prob_thrs, part, bins_dev, sums_dev, roc_dev, c.stream);
-  else
-    rc = obs_f64 ? run_bins(static_cast<const float *>(prob_dev), static_cast<const double *>(obs_dev), npix, x_min, tables, n_bins,
-                            n_prob_thrs, part, bins_dev, sums_dev, roc_dev, c.stream)
-                 : run_bins(static_cast<const float *>(prob_dev), static_cast<const float *>(obs_dev), npix, x_min, tables, n_bins,
-                            n_prob_thrs, part, bins_dev, sums_dev, roc_dev, c.stream);
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(groups_of(npix, kBinsMaxGroups)) * sizeof(BinsPartial))) return rc;
+  BinsPartial *part = blk.as<BinsPartial>();
+  return with_real(prob_dev, prob_f64 != 0, [&](auto *prob) {
+    return with_real(obs_dev, obs_f64 != 0, [&](auto *obs) {
+      return run_bins(prob, obs, npix, x_min, tables, n_bins, n_prob_thrs, part, bins_dev, sums_dev, roc_dev, c.stream);
+    });
+  });
 }

@@ -434,22 +434,16 @@ extern "C" int psh_proesmans_scale_dev(const void *frames_dev, int f32, size_t c
   ReduceBlock *rb = nullptr;
   if (int rc = reduce_block(&rb)) return rc;
   const int nb = blocks_1d(count);
-  if (f32) {
-    const float *in = static_cast<const float *>(frames_dev);
-    hipLaunchKernelGGL(range_partial<float>, dim3(nb), dim3(kThreads), 0, c.stream, in, count, rb);
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(range_finish, dim3(1), dim3(kThreads), 0, c.stream, rb, nb);
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(scale_frames<float>, dim3(nb), dim3(kThreads), 0, c.stream, in, count, static_cast<const ReduceBlock *>(rb), out_dev);
-  } else {
-    const double *in = static_cast<const double *>(frames_dev);
-    hipLaunchKernelGGL(range_partial<double>, dim3(nb), dim3(kThreads), 0, c.stream, in, count, rb);
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(range_finish, dim3(1), dim3(kThreads), 0, c.stream, rb, nb);
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(scale_frames<double>, dim3(nb), dim3(kThreads), 0, c.stream, in, count, static_cast<const ReduceBlock *>(rb), out_dev);
-  }
-  PSH_HIP(hipGetLastError());
+  if (int rc = with_real(frames_dev, !f32, [&](auto *in) -> int {
+        hipLaunchKernelGGL(range_partial, dim3(nb), dim3(kThreads), 0, c.stream, in, count, rb);
+        PSH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(range_finish, dim3(1), dim3(kThreads), 0, c.stream, rb, nb);
+        PSH_HIP(hipGetLastError());
+        hipLaunchKernelGGL(scale_frames, dim3(nb), dim3(kThreads), 0, c.stream, in, count, static_cast<const ReduceBlock *>(rb), out_dev);
+        PSH_HIP(hipGetLastError());
+        return PSH_OK;
+      }))
+    return rc;
   PSH_HIP(hipMemcpyAsync(range_host, rb->range, 3 * sizeof(double), hipMemcpyDeviceToHost, c.stream));
   PSH_HIP(hipStreamSynchronize(c.stream));
   return PSH_OK;

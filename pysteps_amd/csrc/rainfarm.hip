@@ -195,13 +195,13 @@ __global__ __launch_bounds__(kThreads) void finish(const double *__restrict__ e,
 
 template <typename Out>
 void launch_finish(dim3 grid, hipStream_t stream, const double *e, const double *precip, size_t stride, const double *agg, int m,
-                   int n, int ds, const double *table, int na, int amin, int has_thr, double thr, void *out) {
+                   int n, int ds, const double *table, int na, int amin, int has_thr, double thr, Out *out) {
   if (table && na == 3)
     hipLaunchKernelGGL((finish<Out, 3>), grid, dim3(kThreads), 0, stream, e, precip, stride, agg, m, n, ds, table, na, amin, has_thr,
-                       thr, static_cast<Out *>(out));
+                       thr, out);
   else
     hipLaunchKernelGGL((finish<Out, 0>), grid, dim3(kThreads), 0, stream, e, precip, stride, agg, m, n, ds, table, na, amin, has_thr,
-                       thr, static_cast<Out *>(out));
+                       thr, out);
 }
 
 bool shape_ok(int K, int m, int n, int ds) {
@@ -237,9 +237,9 @@ extern "C" int psh_rainfarm_std_dev(const double *noise_dev, int K, size_t plane
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *partial = nullptr;
-  if (int rc = psh_malloc(&partial, static_cast<size_t>(K) * psh::kPartBlocks * sizeof(psh::dd))) return rc;
-  psh::dd *part = static_cast<psh::dd *>(partial);
+  psh::Scratch partial;
+  if (int rc = partial.alloc(static_cast<size_t>(K) * psh::kPartBlocks * sizeof(psh::dd))) return rc;
+  psh::dd *part = partial.as<psh::dd>();
   double2 *stats = reinterpret_cast<double2 *>(stats_dev);
   const double count = static_cast<double>(plane);
   const dim3 grid(psh::kPartBlocks, K), block(psh::kThreads);
@@ -247,9 +247,7 @@ extern "C" int psh_rainfarm_std_dev(const double *noise_dev, int K, size_t plane
   hipLaunchKernelGGL(psh::std_final<false>, dim3(K), block, 0, c.stream, static_cast<const psh::dd *>(part), psh::kPartBlocks, count, stats);
   hipLaunchKernelGGL(psh::std_partial<true>, grid, block, 0, c.stream, noise_dev, plane, static_cast<const double2 *>(stats), part);
   hipLaunchKernelGGL(psh::std_final<true>, dim3(K), block, 0, c.stream, static_cast<const psh::dd *>(part), psh::kPartBlocks, count, stats);
-  const hipError_t e = hipGetLastError();
-  (void)psh_free(partial);  // stream-ordered
-  PSH_HIP(e);
+  PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
@@ -284,12 +282,9 @@ extern "C" int psh_rainfarm_finish_dev(const double *e_dev, const double *precip
   const int M = m * ds, N = n * ds;
   const size_t stride = precip_planes == 1 ? 0 : static_cast<size_t>(m) * n;
   const dim3 grid((N + psh::kThreads - 1) / psh::kThreads, M, K);
-  if (f32)
-    psh::launch_finish<float>(grid, c.stream, e_dev, precip_dev, stride, agg_dev, m, n, ds, table_dev, na, amin, has_threshold,
-                              threshold, out_dev);
-  else
-    psh::launch_finish<double>(grid, c.stream, e_dev, precip_dev, stride, agg_dev, m, n, ds, table_dev, na, amin, has_threshold,
-                               threshold, out_dev);
+  psh::with_real(out_dev, !f32, [&](auto *out) {
+    psh::launch_finish(grid, c.stream, e_dev, precip_dev, stride, agg_dev, m, n, ds, table_dev, na, amin, has_threshold, threshold, out);
+  });
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }

@@ -217,21 +217,16 @@ extern "C" int psh_rapsd_half_dev(const void *spec_dev, int K, int m, int n, dou
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const int nb = rapsd_bins(m, n), G = groups_for(m), bx = (nb + kRapsdThreads - 1) / kRapsdThreads;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(K) * G * nb * sizeof(dd))) return rc;
-  auto run = [&]() -> int {
-    if (int rc = launch_count(m, n, 0, counts_dev, c.stream)) return rc;
-    hipLaunchKernelGGL(rapsd_partial_half, dim3(bx, G, K), dim3(kRapsdThreads), 0, c.stream,
-                       static_cast<const double2 *>(spec_dev), m, n, nb, static_cast<dd *>(blk));
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rapsd_finish, dim3(bx, K), dim3(kRapsdThreads), 0, c.stream, static_cast<const dd *>(blk), G, nb,
-                       static_cast<const unsigned long long *>(counts_dev), static_cast<double>(m) * n, out_dev);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(K) * G * nb * sizeof(dd))) return rc;
+  if (int rc = launch_count(m, n, 0, counts_dev, c.stream)) return rc;
+  hipLaunchKernelGGL(rapsd_partial_half, dim3(bx, G, K), dim3(kRapsdThreads), 0, c.stream,
+                     static_cast<const double2 *>(spec_dev), m, n, nb, blk.as<dd>());
+  PSH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rapsd_finish, dim3(bx, K), dim3(kRapsdThreads), 0, c.stream, blk.as<const dd>(), G, nb,
+                     static_cast<const unsigned long long *>(counts_dev), static_cast<double>(m) * n, out_dev);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 extern "C" int psh_rapsd_full_dev(const void *planes_dev, int f64, int K, int m, int n, double *out_dev,
@@ -245,25 +240,17 @@ extern "C" int psh_rapsd_full_dev(const void *planes_dev, int f64, int K, int m,
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const int nb = rapsd_bins(m, n), G = groups_for(m), bx = (nb + kRapsdThreads - 1) / kRapsdThreads;
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, static_cast<size_t>(K) * G * nb * sizeof(dd))) return rc;
-  auto run = [&]() -> int {
-    if (int rc = launch_count(m, n, 1, counts_dev, c.stream)) return rc;
-    if (f64)
-      hipLaunchKernelGGL(rapsd_partial_full<double>, dim3(bx, G, K), dim3(kRapsdThreads), 0, c.stream,
-                         static_cast<const double *>(planes_dev), m, n, nb, static_cast<dd *>(blk));
-    else
-      hipLaunchKernelGGL(rapsd_partial_full<float>, dim3(bx, G, K), dim3(kRapsdThreads), 0, c.stream,
-                         static_cast<const float *>(planes_dev), m, n, nb, static_cast<dd *>(blk));
-    PSH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rapsd_finish, dim3(bx, K), dim3(kRapsdThreads), 0, c.stream, static_cast<const dd *>(blk), G, nb,
-                       static_cast<const unsigned long long *>(counts_dev), 1.0, out_dev);
-    PSH_HIP(hipGetLastError());
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);  // stream-ordered
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(static_cast<size_t>(K) * G * nb * sizeof(dd))) return rc;
+  if (int rc = launch_count(m, n, 1, counts_dev, c.stream)) return rc;
+  with_real(planes_dev, f64 != 0, [&](auto *planes) {
+    hipLaunchKernelGGL(rapsd_partial_full, dim3(bx, G, K), dim3(kRapsdThreads), 0, c.stream, planes, m, n, nb, blk.as<dd>());
+  });
+  PSH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rapsd_finish, dim3(bx, K), dim3(kRapsdThreads), 0, c.stream, blk.as<const dd>(), G, nb,
+                     static_cast<const unsigned long long *>(counts_dev), 1.0, out_dev);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
 }
 
 extern "C" int psh_rapsd_nonfinite_dev(const void *in_dev, int f64, size_t count, unsigned long long *counts_host) {
@@ -273,29 +260,21 @@ extern "C" int psh_rapsd_nonfinite_dev(const void *in_dev, int f64, size_t count
   Context &c = ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 2 * sizeof(unsigned long long))) return rc;
-  unsigned long long *acc = static_cast<unsigned long long *>(blk);
-  auto run = [&]() -> int {
-    PSH_HIP(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), c.stream));
-    if (count) {
-      const size_t want = (count + kRapsdThreads - 1) / kRapsdThreads;
-      const unsigned blocks = static_cast<unsigned>(want < 2048 ? want : 2048);
-      if (f64)
-        hipLaunchKernelGGL(rapsd_nonfinite<double>, dim3(blocks), dim3(kRapsdThreads), 0, c.stream,
-                           static_cast<const double *>(in_dev), count, acc);
-      else
-        hipLaunchKernelGGL(rapsd_nonfinite<float>, dim3(blocks), dim3(kRapsdThreads), 0, c.stream,
-                           static_cast<const float *>(in_dev), count, acc);
-      PSH_HIP(hipGetLastError());
-    }
-    PSH_HIP(hipMemcpyAsync(counts_host, acc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  const int rc = run();
-  (void)psh_free(blk);
-  return rc;
+  psh::Scratch blk;
+  if (int rc = blk.alloc(2 * sizeof(unsigned long long))) return rc;
+  unsigned long long *acc = blk.as<unsigned long long>();
+  PSH_HIP(hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), c.stream));
+  if (count) {
+    const size_t want = (count + kRapsdThreads - 1) / kRapsdThreads;
+    const unsigned blocks = static_cast<unsigned>(want < 2048 ? want : 2048);
+    with_real(in_dev, f64 != 0, [&](auto *in) {
+      hipLaunchKernelGGL(rapsd_nonfinite, dim3(blocks), dim3(kRapsdThreads), 0, c.stream, in, count, acc);
+    });
+    PSH_HIP(hipGetLastError());
+  }
+  PSH_HIP(hipMemcpyAsync(counts_host, acc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  return PSH_OK;
 }
 
 extern "C" int psh_rapsd_fill_nan_dev(const void *in_dev, int f64, size_t count, double fill, double *out_dev) {
@@ -308,12 +287,9 @@ extern "C" int psh_rapsd_fill_nan_dev(const void *in_dev, int f64, size_t count,
   PSH_HIP(hipSetDevice(c.device));
   const size_t want = (count + kRapsdThreads - 1) / kRapsdThreads;
   const unsigned blocks = static_cast<unsigned>(want < 4096 ? want : 4096);
-  if (f64)
-    hipLaunchKernelGGL(rapsd_fill_nan<double>, dim3(blocks), dim3(kRapsdThreads), 0, c.stream,
-                       static_cast<const double *>(in_dev), count, fill, out_dev);
-  else
-    hipLaunchKernelGGL(rapsd_fill_nan<float>, dim3(blocks), dim3(kRapsdThreads), 0, c.stream,
-                       static_cast<const float *>(in_dev), count, fill, out_dev);
+  with_real(in_dev, f64 != 0, [&](auto *in) {
+    hipLaunchKernelGGL(rapsd_fill_nan, dim3(blocks), dim3(kRapsdThreads), 0, c.stream, in, count, fill, out_dev);
+  });
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }

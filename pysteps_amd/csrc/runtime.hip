@@ -549,7 +549,9 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
   a.outval = outval;
   a.coef = nullptr;
   a.minval = 0.f;
-  void *spline_blk = nullptr;
+  // (destroyed in reverse order: the spline block goes back to the allocator first, then the packed one, both
+  // stream-ordered behind the launch at the end)
+  psh::Scratch packed_blk, spline_blk;
   if (interp_order == 3 && precip_dev) {
     // cubic B-spline coefficients (spline.hip) + the minimum the mask logic restores (:146-147).  Per boundary
     // mode: the filter's boundary kind, and for the two modes SciPy pads before filtering the padded plane
@@ -561,8 +563,8 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
     const size_t plane_bytes = static_cast<size_t>(m + 2 * npad) * (n + 2 * npad) * sizeof(float);
     hipError_t e = hipSuccess;
     if (!all_nan) {
-      if (int rc = psh_malloc(&spline_blk, 2 * plane_bytes)) return rc;
-      float *coef = static_cast<float *>(spline_blk);
+      if (int rc = spline_blk.alloc(2 * plane_bytes)) return rc;
+      float *coef = spline_blk.as<float>();
       float *tmp = coef + plane_bytes / sizeof(float);
       e = psh::spline_prefilter(precip_dev, coef, tmp, m, n, c.stream, kind, npad, mode == PSH_MODE_NEAREST, outval,
                                 a.spline_order);
@@ -572,13 +574,9 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
     double mn = 0.0;
     int rc = e == hipSuccess ? psh_field_stats_dev(precip_dev, static_cast<size_t>(m) * n, &mn, nullptr, nullptr)
                              : fail(PSH_EHIP, "spline prefilter failed: %s", hipGetErrorString(e));
-    if (rc) {
-      if (spline_blk) (void)psh_free(spline_blk);
-      return rc;
-    }
+    if (rc) return rc;
     a.minval = static_cast<float>(mn);
   }
-  void *packed_blk = nullptr;
   if (psh::semilag_wants_packed(a)) {
     // {u,v} interleaved copy of the velocity for the dwordx4 gathers (semilag.hip); cached block
     // and, for bilinear resampling over several lead times, the row-pair copy of the field behind it
@@ -586,28 +584,21 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
     const bool pairs = psh::semilag_wants_field_pairs(a);
     const bool own_uv = velocity_uv_dev == nullptr || reinterpret_cast<uintptr_t>(velocity_uv_dev) % 16 != 0;
     int rc = PSH_OK;
-    if (own_uv || pairs) rc = psh_malloc(&packed_blk, ((own_uv ? 2 : 0) + (pairs ? 2 : 0)) * plane * sizeof(float));
+    if (own_uv || pairs) rc = packed_blk.alloc(((own_uv ? 2 : 0) + (pairs ? 2 : 0)) * plane * sizeof(float));
     if (rc == PSH_OK) {
       hipError_t pe = hipSuccess;
-      if (own_uv) pe = psh::launch_pack_velocity(velocity_dev, static_cast<float *>(packed_blk), plane, c.stream);
+      if (own_uv) pe = psh::launch_pack_velocity(velocity_dev, packed_blk.as<float>(), plane, c.stream);
       if (pe == hipSuccess && pairs) {
-        float *pp = static_cast<float *>(packed_blk) + (own_uv ? 2 : 0) * plane;
+        float *pp = packed_blk.as<float>() + (own_uv ? 2 : 0) * plane;
         pe = psh::launch_pack_field_rows(precip_dev, pp, m, n, c.stream);
         a.field_pairs = pp;
       }
       if (pe != hipSuccess) rc = fail(PSH_EHIP, "pack_velocity failed: %s", hipGetErrorString(pe));
     }
-    if (rc) {
-      if (packed_blk) (void)psh_free(packed_blk);
-      if (spline_blk) (void)psh_free(spline_blk);
-      return rc;
-    }
-    a.vel_packed = own_uv ? static_cast<const float *>(packed_blk) : velocity_uv_dev;
+    if (rc) return rc;
+    a.vel_packed = own_uv ? packed_blk.as<const float>() : velocity_uv_dev;
   }
-  const hipError_t le = psh::launch_semilag(a, c.stream);
-  if (spline_blk) (void)psh_free(spline_blk);  // stream-ordered: the launch above is queued first
-  if (packed_blk) (void)psh_free(packed_blk);
-  PSH_HIP(le);
+  PSH_HIP(psh::launch_semilag(a, c.stream));
   return PSH_OK;
 }
 

@@ -299,25 +299,19 @@ extern "C" int psh_outliers_local_host(const double *xy, const double *values, i
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const size_t vec_bytes = static_cast<size_t>(n) * 2 * sizeof(double);
-  void *blk = nullptr;
-  if (int rc = psh_malloc(&blk, 2 * vec_bytes + static_cast<size_t>(n))) return rc;
-  char *base = static_cast<char *>(blk);
+  psh::Scratch blk;
+  if (int rc = blk.alloc(2 * vec_bytes + static_cast<size_t>(n))) return rc;
+  char *base = blk.as<char>();
   double2 *d_xy = reinterpret_cast<double2 *>(base);
   double2 *d_uv = reinterpret_cast<double2 *>(base + vec_bytes);
   unsigned char *d_fl = reinterpret_cast<unsigned char *>(base + 2 * vec_bytes);
-  int rc = PSH_OK;
-  auto run = [&]() -> int {
-    PSH_HIP(hipMemcpyAsync(d_xy, xy, vec_bytes, hipMemcpyHostToDevice, c.stream));
-    PSH_HIP(hipMemcpyAsync(d_uv, values, vec_bytes, hipMemcpyHostToDevice, c.stream));
-    psh::launch_outliers(n, static_cast<size_t>(n), c.stream, d_xy, d_uv, n, nullptr, k, thr, d_fl);
-    PSH_HIP(hipGetLastError());
-    PSH_HIP(hipMemcpyAsync(flags, d_fl, static_cast<size_t>(n), hipMemcpyDeviceToHost, c.stream));
-    PSH_HIP(hipStreamSynchronize(c.stream));
-    return PSH_OK;
-  };
-  rc = run();
-  (void)psh_free(blk);
-  return rc;
+  PSH_HIP(hipMemcpyAsync(d_xy, xy, vec_bytes, hipMemcpyHostToDevice, c.stream));
+  PSH_HIP(hipMemcpyAsync(d_uv, values, vec_bytes, hipMemcpyHostToDevice, c.stream));
+  psh::launch_outliers(n, static_cast<size_t>(n), c.stream, d_xy, d_uv, n, nullptr, k, thr, d_fl);
+  PSH_HIP(hipGetLastError());
+  PSH_HIP(hipMemcpyAsync(flags, d_fl, static_cast<size_t>(n), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  return PSH_OK;
 }
 
 // ---------------------------------------------------------------------------

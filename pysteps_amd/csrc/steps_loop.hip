@@ -588,15 +588,13 @@ extern "C" int psh_steps_mean_shift_dev(double *field_dev, size_t n, double thre
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const int nparts = 1024;
-  void *partial = nullptr;
-  if (int rc = psh_malloc(&partial, nparts * sizeof(double2))) return rc;
+  psh::Scratch partial;
+  if (int rc = partial.alloc(nparts * sizeof(double2))) return rc;
   hipLaunchKernelGGL(psh::wet_sum, dim3(nparts), dim3(psh::kThreads), 0, c.stream, field_dev, n, threshold,
-                     static_cast<double2 *>(partial));
+                     partial.as<double2>());
   hipLaunchKernelGGL(psh::mean_shift, dim3(psh::grid_for(n)), dim3(psh::kThreads), 0, c.stream, field_dev, n, threshold, mu_0,
-                     static_cast<const double2 *>(partial), nparts);
-  const hipError_t e = hipGetLastError();
-  (void)psh_free(partial);  // stream-ordered
-  PSH_HIP(e);
+                     partial.as<const double2>(), nparts);
+  PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
@@ -647,15 +645,13 @@ extern "C" int psh_steps_spectral_sums_dev(const void *noise_spec_dev, const dou
   PSH_HIP(hipSetDevice(c.device));
   const int nc = n / 2 + 1;
   const int grid = std::min(m, 1024);  // rows are dealt to the workgroups
-  void *partial = nullptr;
-  if (int rc = psh_malloc(&partial, static_cast<size_t>(grid) * psh::kMaxLevels * sizeof(double))) return rc;
+  psh::Scratch partial;
+  if (int rc = partial.alloc(static_cast<size_t>(grid) * psh::kMaxLevels * sizeof(double))) return rc;
   hipLaunchKernelGGL(psh::spectral_level_sums, dim3(grid), dim3(psh::kThreads), 0, c.stream, static_cast<const double2 *>(noise_spec_dev),
-                     filter_dev, weights_dev, nlevels, m, nc, (n & 1) == 0 ? 1 : 0, static_cast<double *>(partial));
+                     filter_dev, weights_dev, nlevels, m, nc, (n & 1) == 0 ? 1 : 0, partial.as<double>());
   hipLaunchKernelGGL(psh::spectral_level_sums_final, dim3(psh::kMaxLevels), dim3(psh::kThreads), 0, c.stream,
-                     static_cast<const double *>(partial), grid, sums_dev);
-  const hipError_t e = hipGetLastError();
-  (void)psh_free(partial);  // stream-ordered
-  PSH_HIP(e);
+                     partial.as<const double>(), grid, sums_dev);
+  PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
