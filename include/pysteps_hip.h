@@ -97,10 +97,19 @@ int psh_event_elapsed_ms(void *start, void *stop, float *ms); /* waits for stop 
 /* ---- element-wise passes either side of the path (keep a nowcast chain in HBM) ------ *
  * psh_db_transform_dev: pysteps/utils/transformation.py:150-232 (dB_transform).  Forward:
  *   out = R < threshold ? zerovalue : 10 log10(R)  (threshold in the units of R);  inverse:
- *   out = 10^(R/10) < 10^(threshold/10) ? zerovalue : 10^(R/10)  (threshold in dB).  n floats,
- *   in place allowed, NaN stays NaN.
- * psh_field_stats_dev: min / max over the finite values and the number of non-finite values
- *   (the NumPy scans of nowcasts/extrapolation.py:76 and semilagrangian.py:171-172). Synchronous. */
+ *   out = 10^(R/10) < threshold ? zerovalue : 10^(R/10)  (threshold LINEAR: the caller forms
+ *   10^(dB/10) the way the reference does, :227).  Both comparisons run in double, so `threshold`
+ *   is the number NumPy would compare a float32 array with: the caller rounds it to float32 first
+ *   where NumPy would (a Python float, a numpy.float32) and passes it as it is where NumPy
+ *   compares in float64 (a numpy.float64 scalar, which is what metadata["threshold"] holds after
+ *   a forward transform).  n floats, in place allowed, NaN stays NaN.  Buffers that are both
+ *   16-byte aligned take the dwordx4 path; any other 4-byte aligned pair (a plane of a stack whose
+ *   planes are not a multiple of four pixels) takes a one-element-per-thread path with the same
+ *   arithmetic, so a value's result does not depend on where it lies.
+ * psh_field_stats_dev: min / max over the finite values, the number of non-finite values and
+ *   np.nanmin (an infinity is a value; NaN if every value is NaN) - the NumPy scans of
+ *   nowcasts/extrapolation.py:76 and semilagrangian.py:171-172.  Any output may be NULL.
+ *   Synchronous. */
 int psh_db_transform_dev(const float *in_dev, float *out_dev, size_t n, double threshold,
                          double zerovalue, int inverse);
 /* float64 <-> float32 element conversion on the device (to_f64 != 0: float32 -> float64), so that
@@ -117,7 +126,7 @@ int psh_count_above_dev(const float *in_dev, size_t n, double threshold, double 
 /* number of NaN / infinite values of a float64 device array (waits for the result) */
 int psh_nonfinite_count_f64_dev(const double *in_dev, size_t n, double *count_out);
 int psh_field_stats_dev(const float *in_dev, size_t n, double *min_out, double *max_out,
-                        double *nonfinite_out);
+                        double *nonfinite_out, double *nanmin_out);
 
 /* ---- semi-Lagrangian extrapolation ------------------------------------- *
  * Replaces pysteps/extrapolation/semilagrangian.py:21-266 (extrapolate) incl.

@@ -32,6 +32,7 @@ from .. import _lib
 from .._reference import decline, lookup
 from .._reference import method as reference_method
 from ..device import DeviceArray
+from ..utils.transformation import _transform_dev
 
 __all__ = ["forecast", "blend", "weight_schedule", "member_maps", "to_rainrate"]
 
@@ -90,12 +91,12 @@ def to_rainrate(field, metadata):
     lib = _lib.lib()
     out = field
     if metadata["transform"] == "dB":
-        threshold = float(metadata.get("threshold", -10.0))
-        out = DeviceArray(field.shape, field.dtype)
         if field.dtype == np.float32:
-            _lib.check(lib.psh_db_transform_dev(field.ptr, out.ptr, field.size, threshold, 0.0, 1), "psh_db_transform_dev")
+            out = _transform_dev(field, 10.0 ** (metadata.get("threshold", -10.0) / 10.0), 0.0, True)
         else:
-            _lib.check(lib.psh_blend_db_inverse_f64_dev(field.ptr, out.ptr, field.size, threshold, 0.0),
+            out = DeviceArray(field.shape, field.dtype)
+            _lib.check(lib.psh_blend_db_inverse_f64_dev(field.ptr, out.ptr, field.size,
+                                                        float(metadata.get("threshold", -10.0)), 0.0),
                        "psh_blend_db_inverse_f64_dev")
     if metadata["unit"] == "mm":
         src = out

@@ -13,32 +13,40 @@
 namespace psh {
 namespace {
 
-__device__ __forceinline__ float to_db(float r, float thr, float zerovalue) {
+// the `<` of both directions runs in double against the number NumPy would compare with: a Python float or a
+// numpy.float32 meets a float32 field in float32, a numpy.float64 scalar in float64; the caller rounds the threshold
+// accordingly (device._compared_as) and the float32 value widens exactly, so one comparison serves both
+__device__ __forceinline__ float to_db(float r, double thr, float zerovalue) {
   // R[~(R < thr)] = 10 log10(R); R[R < thr] = zerovalue  (NaN compares false -> log10(NaN) = NaN)
-  return r < thr ? zerovalue : 10.0f * log10f(r);
+  return static_cast<double>(r) < thr ? zerovalue : 10.0f * log10f(r);
 }
-__device__ __forceinline__ float from_db(float r, float thr_lin, float zerovalue) {
+__device__ __forceinline__ float from_db(float r, double thr_lin, float zerovalue) {
   const float v = exp10f(r / 10.0f);
-  return v < thr_lin ? zerovalue : v;
+  return static_cast<double>(v) < thr_lin ? zerovalue : v;
 }
 
-template <bool INVERSE>
+// VEC: dwordx4 body and a scalar tail (both buffers 16-byte aligned); otherwise one element per thread with the same
+// arithmetic, for planes that start off alignment (view(k) of a stack whose planes are not a multiple of four pixels)
+template <bool INVERSE, bool VEC>
 __global__ __launch_bounds__(256) void db_transform(const float *__restrict__ in,
-                                                    float *__restrict__ out, size_t n, float thr,
+                                                    float *__restrict__ out, size_t n, double thr,
                                                     float zerovalue) {
   const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  const size_t n4 = n / 4;
-  const float4 *in4 = reinterpret_cast<const float4 *>(in);
-  float4 *out4 = reinterpret_cast<float4 *>(out);
-  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 v = in4[i];
-    v.x = INVERSE ? from_db(v.x, thr, zerovalue) : to_db(v.x, thr, zerovalue);
-    v.y = INVERSE ? from_db(v.y, thr, zerovalue) : to_db(v.y, thr, zerovalue);
-    v.z = INVERSE ? from_db(v.z, thr, zerovalue) : to_db(v.z, thr, zerovalue);
-    v.w = INVERSE ? from_db(v.w, thr, zerovalue) : to_db(v.w, thr, zerovalue);
-    out4[i] = v;
+  const size_t first = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const size_t n4 = VEC ? n / 4 : 0;
+  if (VEC) {
+    const float4 *in4 = reinterpret_cast<const float4 *>(in);
+    float4 *out4 = reinterpret_cast<float4 *>(out);
+    for (size_t i = first; i < n4; i += stride) {
+      float4 v = in4[i];
+      v.x = INVERSE ? from_db(v.x, thr, zerovalue) : to_db(v.x, thr, zerovalue);
+      v.y = INVERSE ? from_db(v.y, thr, zerovalue) : to_db(v.y, thr, zerovalue);
+      v.z = INVERSE ? from_db(v.z, thr, zerovalue) : to_db(v.z, thr, zerovalue);
+      v.w = INVERSE ? from_db(v.w, thr, zerovalue) : to_db(v.w, thr, zerovalue);
+      out4[i] = v;
+    }
   }
-  for (size_t i = n4 * 4 + static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride)
+  for (size_t i = n4 * 4 + first; i < n; i += stride)
     out[i] = INVERSE ? from_db(in[i], thr, zerovalue) : to_db(in[i], thr, zerovalue);
 }
 
@@ -167,21 +175,19 @@ extern "C" int psh_db_transform_dev(const float *in_dev, float *out_dev, size_t 
   PSH_REQUIRE_INIT();
   if (n == 0) return PSH_OK;
   if (!in_dev || !out_dev) return psh::fail(PSH_EINVAL, "db_transform: NULL pointer");
-  if ((reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15)
-    return psh::fail(PSH_EINVAL, "db_transform: buffers must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3)
+    return psh::fail(PSH_EINVAL, "db_transform: buffers must be 4-byte aligned");
+  const bool vec = ((reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) == 0;
   psh::Context &c = psh::ctx();
   std::lock_guard<std::recursive_mutex> lock(c.mu);
   PSH_HIP(hipSetDevice(c.device));
   const dim3 grid(c.cu_count * 8), block(256);
-  if (inverse) {
-    // threshold is given in dB and compared in linear units (transformation.py:225-226)
-    const float thr_lin = static_cast<float>(pow(10.0, threshold / 10.0));
-    hipLaunchKernelGGL(psh::db_transform<true>, grid, block, 0, c.stream, in_dev, out_dev, n, thr_lin,
-                       static_cast<float>(zerovalue));
-  } else {
-    hipLaunchKernelGGL(psh::db_transform<false>, grid, block, 0, c.stream, in_dev, out_dev, n,
-                       static_cast<float>(threshold), static_cast<float>(zerovalue));
-  }
+  // threshold: the number each value is compared with, in the units of the values compared (forward: of R; inverse:
+  // linear, of 10^(R/10) - transformation.py:227-228), already rounded the way NumPy would round it
+  const float zv = static_cast<float>(zerovalue);
+  auto kernel = inverse ? (vec ? psh::db_transform<true, true> : psh::db_transform<true, false>)
+                        : (vec ? psh::db_transform<false, true> : psh::db_transform<false, false>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, c.stream, in_dev, out_dev, n, threshold, zv);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
@@ -325,7 +331,7 @@ extern "C" int psh_convert_dev(const void *in_dev, void *out_dev, size_t n, int 
 }
 
 extern "C" int psh_field_stats_dev(const float *in_dev, size_t n, double *min_out, double *max_out,
-                                   double *nonfinite_out) {
+                                   double *nonfinite_out, double *nanmin_out) {
   PSH_REQUIRE_INIT();
   if (!in_dev && n) return psh::fail(PSH_EINVAL, "field_stats: NULL pointer");
   psh::Context &c = psh::ctx();
@@ -336,5 +342,6 @@ extern "C" int psh_field_stats_dev(const float *in_dev, size_t n, double *min_ou
   if (min_out) *min_out = st.min_finite;   // +inf if there is no finite value
   if (max_out) *max_out = st.max_finite;   // -inf if there is no finite value
   if (nonfinite_out) *nonfinite_out = st.nonfinite;
+  if (nanmin_out) *nanmin_out = st.nanmin();  // np.nanmin: an infinity is a value, NaN if there is none at all
   return PSH_OK;
 }

@@ -261,7 +261,7 @@ int psh_set_option(const char *key, int value) {
 }
 
 int psh_field_stats_dev(const float *in_dev, size_t n, double *min_out, double *max_out,
-                        double *nonfinite_out);
+                        double *nonfinite_out, double *nanmin_out);
 
 int psh_device_info(int *device_id, int *cu_count, size_t *hbm_total, size_t *hbm_free,
                     char *name, int name_len) {
@@ -572,7 +572,7 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
       a.coef_pad = npad;
     }
     double mn = 0.0;
-    int rc = e == hipSuccess ? psh_field_stats_dev(precip_dev, static_cast<size_t>(m) * n, &mn, nullptr, nullptr)
+    int rc = e == hipSuccess ? psh_field_stats_dev(precip_dev, static_cast<size_t>(m) * n, &mn, nullptr, nullptr, nullptr)
                              : fail(PSH_EHIP, "spline prefilter failed: %s", hipGetErrorString(e));
     if (rc) return rc;
     a.minval = static_cast<float>(mn);

@@ -303,9 +303,9 @@ def _run_device(lib, precip, velocity, steps, outval, displacement_prev, n_iter,
     if isinstance(outval, str):
         if outval != "min":
             raise ValueError("outval must be a number or 'min'")
-        from ..utils.transformation import field_stats  # noqa: PLC0415
+        from ..utils.transformation import field_nanmin  # noqa: PLC0415
 
-        outval = field_stats(precip)[0] if precip is not None else float("nan")  # device reduction
+        outval = field_nanmin(precip) if precip is not None else float("nan")  # device reduction, np.nanmin (:171-172)
     disp = None
     resume = 0
     if displacement_prev is not None:
