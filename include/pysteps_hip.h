@@ -449,6 +449,29 @@ int psh_probbins_dev(const void *prob_dev, int prob_f64, const void *obs_dev, in
                      const double *edges_host, int n_edges, const double *prob_thrs_host, int n_prob_thrs,
                      unsigned long long *bins_dev, double *sums_dev, unsigned long long *roc_dev);
 
+/* ---- ensemble spread: all pairs of members in one pass (csrc/ensscores.hip) ---------------------------------------- *
+ * pysteps/verification/ensscores.py ensemble_spread for a stack of K members (2..64) of npix contiguous pixels, float32
+ * or float64 (f64).  The K (K - 1) / 2 pairs (i, j), i < j, are numbered in the reference's loop order, i outer and j
+ * inner; member i is the prediction, member j the observation.  Both calls are queued on the library stream and return
+ * the same bits in every run and wherever the stack lies.
+ *
+ * psh_detcat_pairs_dev: an event is value > thr_host[t], compared as float64 (the caller decides what a threshold
+ * stands for against a float32 stack), NaN compares false.  hits_dev (n_thresholds, pairs) receives the number of
+ * pixels where both members of a pair have the event, events_dev (n_thresholds, K) every member's number of events:
+ * false alarms of (i, j) = events[i] - hits, misses = events[j] - hits, correct negatives = npix - events[i] -
+ * events[j] + hits.  The host table is consumed before the call returns.
+ *
+ * psh_detcont_pairs_dev: counts_dev (pairs) receives the number of pixels of a pair whose residual member i - member j
+ * is finite, sums_dev (pairs, 7, 2) the first seven sums of psh_detcont_sums_dev (res, res^2, |res|, (pred + obs)^2,
+ * obs, pred and obs * pred over those pixels) as (hi, lo): bit 1 << s of sum_mask (1..127) selects sum s, the others
+ * come back as zeros.  A selected sum holds the bits psh_detcont_sums_dev returns for (member i, member j) without
+ * conditioning; each member's own sums and its count of infinite values come from that call with the stack on both
+ * sides. */
+int psh_detcat_pairs_dev(const void *stack_dev, int f64, int K, size_t npix, const double *thr_host, int n_thresholds,
+                         unsigned long long *hits_dev, unsigned long long *events_dev);
+int psh_detcont_pairs_dev(const void *stack_dev, int f64, int K, size_t npix, int sum_mask, unsigned long long *counts_dev,
+                          double *sums_dev);
+
 /* ---- radially averaged power spectra (csrc/rapsd.hip) --------------------------------------------------------- *
  * pysteps/utils/spectral.py:100-180 (rapsd) for a stack of K planes: the mean power over the coefficients of every
  * integer radius r = round(sqrt(kx^2 + ky^2)) < nb, with l = max(m, n) and nb = l / 2 (+ 1 for odd l).  out_dev

@@ -116,6 +116,8 @@ SIGNATURES = {
     "psh_crps_sums_dev": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
     "psh_probbins_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_size_t, c_double, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                  c_void_p, c_void_p]),
+    "psh_detcat_pairs_dev": (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
+    "psh_detcont_pairs_dev": (c_int, [c_void_p, c_int, c_int, c_size_t, c_int, c_void_p, c_void_p]),
     "psh_rapsd_half_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "psh_rapsd_full_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "psh_rapsd_counts_dev": (c_int, [c_int, c_int, c_int, c_void_p]),

@@ -75,6 +75,9 @@ SWAPS = (
     # get_method imports CRPS, reldiag and ROC_curve from the module when it is called (interface.py:239); the _init
     # and _compute functions stay the reference's: objects of either side are interchangeable
     ("probscores", "verification.probscores", "SWAPPED", "verification:"),
+    # get_method(..., type="ensemble") imports ensemble_skill and ensemble_spread from the module when it is called
+    # (interface.py:227); rankhist stays the reference's (its ties are broken at random)
+    ("ensscores", "verification.ensscores", ("ensemble_skill", "ensemble_spread"), "verification:"),
     # nowcasts.steps(noise_stddev_adj="auto") looks noise.utils.compute_noise_stddev_adjs up when it is called
     # (nowcasts/steps.py:760)
     ("noise_stddev_adj", "noise.utils", ("compute_noise_stddev_adjs",), "noise.utils:"),

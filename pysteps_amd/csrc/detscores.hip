@@ -22,45 +22,16 @@
 // npix is odd for float64) and element by element otherwise and at the member's ragged end.
 #include "common.h"
 #include "dd.h"
+#include "detsums.h"
 
 namespace psh {
 namespace {
 
-constexpr int kDetThreads = 256;
-constexpr int kDetMaxGroups = 512;  // workgroups per member - fixed: the summation order is part of the result
 constexpr int kDetThrBlock = 8;     // thresholds per pass of detcat_count
 constexpr int kDetSums = 11;
 constexpr int kDetCounts = 4;       // finite observations, finite predictions, finite pairs, +-inf values seen
 
-enum { kSumRes = 0, kSumRes2, kSumAbs, kSumSum2, kSumObsPair, kSumPredPair, kSumObsPred, kSumObs, kSumObs2, kSumPred, kSumPred2 };
-
-__device__ __forceinline__ double quiet_nan() { return __builtin_nan(""); }
-
-// four consecutive pixels from element i (a multiple of 4) as float64; beyond npix: NaN (counts nowhere)
-__device__ __forceinline__ void load4(const float *__restrict__ p, size_t i, size_t npix, bool vec, double (&x)[4]) {
-  if (vec && i + 4 <= npix) {
-    const float4 v = *reinterpret_cast<const float4 *>(p + i);
-    x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = i + j < npix ? static_cast<double>(p[i + j]) : quiet_nan();
-  }
-}
-__device__ __forceinline__ void load4(const double *__restrict__ p, size_t i, size_t npix, bool vec, double (&x)[4]) {
-  if (vec && i + 4 <= npix) {
-    const double2 a = *reinterpret_cast<const double2 *>(p + i);
-    const double2 b = *reinterpret_cast<const double2 *>(p + i + 2);
-    x[0] = a.x, x[1] = a.y, x[2] = b.x, x[3] = b.y;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = i + j < npix ? p[i + j] : quiet_nan();
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ bool aligned16(const T *p) {
-  return (reinterpret_cast<uintptr_t>(p) & 15u) == 0;
-}
+enum { kSumObs = kPairSums, kSumObs2, kSumPred, kSumPred2 };  // after the pair sums of detsums.h: each field's own
 
 struct DetThresholds {
   double f[kDetThrBlock], o[kDetThrBlock];
@@ -130,15 +101,6 @@ struct DetPartial {
   dd sum[kDetSums];
   unsigned long long count[kDetCounts];
 };
-
-__device__ __forceinline__ dd dd_add_prod(dd a, double x, double y) {  // a + x * y, the product exact
-#pragma clang fp contract(off)
-  const double p = x * y;
-  const double e = fma(x, y, -p);
-  dd t = two_sum(a.hi, p);
-  t.lo = t.lo + (a.lo + e);
-  return quick_two_sum(t.hi, t.lo);
-}
 
 // grid (groups, K); partial[member][group]
 template <typename TF, typename TO>
@@ -241,11 +203,6 @@ __global__ __launch_bounds__(64) void detcont_finish(const DetPartial *__restric
     for (int d = 32; d >= 1; d >>= 1) t += __shfl_xor(t, d);
     if (lane == 0) counts[static_cast<size_t>(blockIdx.x) * kDetCounts + s] = t;
   }
-}
-
-int det_groups(size_t npix) {
-  const size_t chunks = (npix + 3) / 4, groups = (chunks + kDetThreads - 1) / kDetThreads;
-  return static_cast<int>(groups < static_cast<size_t>(kDetMaxGroups) ? groups : kDetMaxGroups);
 }
 
 template <typename TF, typename TO>

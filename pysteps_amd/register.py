@@ -238,6 +238,17 @@ def unpatch_probscores():
     unpatch("probscores")
 
 
+def patch_ensscores():
+    """Replace ``ensemble_skill`` and ``ensemble_spread`` of ``pysteps.verification.ensscores`` by the device versions
+    (:mod:`pysteps_amd.verification.ensscores`); ``rankhist`` stays the reference's."""
+    return patch("ensscores")
+
+
+def unpatch_ensscores():
+    """Undo :func:`patch_ensscores`."""
+    unpatch("ensscores")
+
+
 def patch_noise_stddev_adj():
     """Replace ``pysteps.noise.utils.compute_noise_stddev_adjs`` by the device version
     (:mod:`pysteps_amd.noise.utils`); calls the device path declines run the reference's function with a
@@ -320,7 +331,8 @@ def register_postprocessing(override=False):
 
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
-             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False, rapsd=False, probscores=False):
+             dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False, rapsd=False, probscores=False,
+             ensscores=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -342,7 +354,9 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     undoes it).  ``rapsd=True`` makes ``pysteps.utils.spectral.rapsd`` bin its spectra on the device
     (:func:`patch_rapsd`; :func:`unpatch_rapsd` undoes it).  ``probscores=True`` makes
     ``pysteps.verification.probscores`` accumulate the CRPS, reliability diagrams and ROC curves on the device
-    (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it).
+    (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it).  ``ensscores=True`` makes
+    ``pysteps.verification.ensscores`` compute ensemble skill and spread on the device (:func:`patch_ensscores`;
+    :func:`unpatch_ensscores` undoes it).
 
     ``"rainfarm_hip"`` joins ``pysteps.downscaling``'s method table (:func:`register_downscaling`), and
     ``"linear_blending_hip"`` and ``"salient_blending_hip"`` join ``pysteps.blending``'s (:func:`register_blending`)."""
@@ -375,7 +389,7 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += register_spectral()
     for key, wanted in (("probmatching", probmatching), ("autoregression", autoregression), ("dilated_mask", dilated_mask),
                         ("fss", fss), ("noise_stddev_adj", noise_stddev_adj), ("detscores", detscores), ("rapsd", rapsd),
-                        ("probscores", probscores)):
+                        ("probscores", probscores), ("ensscores", ensscores)):
         if wanted:
             added += patch(key)
     if patch_main_loop:

@@ -1,13 +1,14 @@
 """Mirrors of pysteps.verification scores that run on the device; ``get_method`` mirrors
 pysteps/verification/interface.py for the names this package serves."""
 
-from . import detcatscores, detcontscores, probscores, spatialscores  # noqa: F401
+from . import detcatscores, detcontscores, ensscores, probscores, spatialscores  # noqa: F401
 from .._registry import MethodTable
 from .detcatscores import (det_cat_fct, det_cat_fct_accum, det_cat_fct_compute, det_cat_fct_init, det_cat_fct_merge,  # noqa: F401
                            det_cat_table)
 from .detcontscores import (det_cont_fct, det_cont_fct_accum, det_cont_fct_compute, det_cont_fct_init,  # noqa: F401
                             det_cont_fct_merge, det_cont_table)
 from .detscores import DetScoresAccumulator  # noqa: F401
+from .ensscores import SpreadSkillAccumulator, ensemble_skill, ensemble_spread, pair_scores  # noqa: F401
 from .probscores import (CRPS, CRPS_accum, CRPS_compute, CRPS_init, ProbScoresAccumulator, ROC_curve, ROC_curve_accum,  # noqa: F401
                          ROC_curve_compute, ROC_curve_init, crps_table, reldiag, reldiag_accum, reldiag_compute, reldiag_init)
 from .spatialscores import FssAccumulator, fss, fss_accum, fss_compute, fss_init, fss_merge, fss_table  # noqa: F401

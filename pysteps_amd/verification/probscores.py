@@ -28,7 +28,7 @@ against several observations, or several stacks, in one call.
 
 ``ensscores.rankhist`` has no device version on purpose: the reference breaks ties with unseeded
 ``np.random.uniform`` (ensscores.py:245) and precipitation ensembles are mostly ties, so its result is not a function
-of its input.  ``ensemble_skill`` and ``ensemble_spread`` stay the reference's as well.
+of its input.
 """
 
 import ctypes
