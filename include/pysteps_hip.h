@@ -988,6 +988,37 @@ int psh_masked_moments_dev(const double *planes_dev, int nplanes, size_t plane, 
 int psh_spectrum_level_moments_dev(const void *spec_dev, int nspec, const double *weights_dev, int nlevels, int m, int n,
                                    double *stats_dev);
 
+/* ---- temporal autocorrelation of a cascade (csrc/autocorr.hip) ---------------------------------------------- *
+ * pysteps/timeseries/correlation.py (temporal_autocorrelation): every cascade level and every lag from one read of
+ * the stack.  Sums are double-double pairs {hi, lo} with exact products; block partial sums are finished by one block
+ * in a fixed order (no floating-point atomics; the counts are integer atomics): identical bits from run to run, for
+ * any number of levels and wherever the stack lies.  d = 1: x[t+1] - x[t] (np.diff) is formed in registers in
+ * float64; K = nframes - d - 1 lags, 1..8.  Asynchronous.
+ *  psh_autocorr_sums_dev           stack (nlevels, nframes, npix), float64 or float32 (widened); mask: npix bytes
+ *      shared by the levels, NULL = every pixel.  With a = x[-1], b_k = x[-(k+2)] over the masked pixels:
+ *      sums[l] = {sum a, sum a^2, then per lag sum b_k, sum b_k^2, sum a b_k}: (nlevels, 2 + 3 K, 2) doubles.
+ *      *count_dev = masked pixels; nonfinite_dev[l] = non-finite values among ALL pixels of the level's nframes planes
+ *  psh_autocorr_spectral_sums_dev  spectra (nlevels, nframes, m, nc) complex128 of fields (m, n): nc = n/2+1, or n
+ *      with full_fft.  sums[l] = {sum h |X|^2, then per lag Re sum h X conj(Y_k), sum h |Y_k|^2}: (nlevels, 1 + 2 K, 2)
+ *      doubles; h = 1 on column 0 and on the Nyquist column of an even n, 2 elsewhere, 1 everywhere with full_fft
+ *      (pysteps/utils/spectral.py:62-76; the DC terms are the caller's).  nonfinite_dev[l] as above, per complex value
+ *  psh_autocorr_window_prepare_dev float64 stack (nframes, npix) -> out (1 + nframes - d, npix): out[0] =
+ *      mask.astype(float), then the (differenced) planes in time order with x[~mask] = 0.0 (correlation.py:232-236);
+ *      *nonfinite_dev = non-finite values of the stack
+ *  psh_window_corrcoef_dev         correlation.py:248-269 on the six gaussian_filter(..., mode="constant") planes of
+ *      mask, x, y, x^2, y^2, x y (psh_anvil_gauss_dev), each multiplied by factor = window_size**2 first; the reference's
+ *      operations in its order, each rounded on its own; NaN where stdx > 1e-8, stdy > 1e-8, stdx * stdy > 1e-8 and
+ *      n >= 3 do not all hold */
+int psh_autocorr_sums_dev(const void *stack_dev, int is_f64, int nlevels, int nframes, size_t npix,
+                          const unsigned char *mask_dev, int d, double *sums_dev, unsigned long long *count_dev,
+                          unsigned long long *nonfinite_dev);
+int psh_autocorr_spectral_sums_dev(const void *spec_dev, int nlevels, int nframes, int m, int nc, int n, int full_fft,
+                                   int d, double *sums_dev, unsigned long long *nonfinite_dev);
+int psh_autocorr_window_prepare_dev(const double *stack_dev, int nframes, size_t npix, const unsigned char *mask_dev,
+                                    int d, double *out_dev, unsigned long long *nonfinite_dev);
+int psh_window_corrcoef_dev(const double *n_dev, const double *sx_dev, const double *sy_dev, const double *ssx_dev,
+                            const double *ssy_dev, const double *sxy_dev, double factor, size_t count, double *out_dev);
+
 /* ---- numpy.random.RandomState.randn on the device (csrc/rng.hip) ------------------ *
  * The white noise of the STEPS member loop: pysteps/noise/fftgenerators.py:400 draws
  * `randstate.randn(m, n)` per member and time step from generators seeded by the chain of

@@ -88,6 +88,10 @@ SIGNATURES = {
     "psh_mask_count_dev": (c_int, [c_void_p, c_size_t, c_void_p]),
     "psh_masked_moments_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
     "psh_spectrum_level_moments_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "psh_autocorr_sums_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "psh_autocorr_spectral_sums_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "psh_autocorr_window_prepare_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_int, c_void_p, c_void_p]),
+    "psh_window_corrcoef_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_size_t, c_void_p]),
     "psh_probmatch_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "psh_probmatch_async_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "psh_probmatch_status": (c_int, [c_int]),

@@ -86,6 +86,10 @@ SWAPS = (
     # reference's downscaling.rainfarm binds the name when it is imported, uses it for spectral fusion alone and keeps
     # the stock function; the device RainFARM hands spectral fusion to the reference and needs no rapsd
     ("rapsd", "utils.spectral", ("rapsd",), "utils.spectral:"),
+    # correlation.temporal_autocorrelation(...) per cascade level in front of the main loops: nowcasts/steps.py:840,
+    # sprog.py:290, sseps.py:445, blending/steps.py:1491, pca_ens_kalman_filter.py:445, and anvil.py's moving-window
+    # form; the multivariate function stays the reference's
+    ("correlation", "timeseries.correlation", ("temporal_autocorrelation",), "correlation:"),
 )
 
 

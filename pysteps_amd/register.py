@@ -272,6 +272,19 @@ def unpatch_rapsd():
     unpatch("rapsd")
 
 
+def patch_correlation():
+    """Replace ``pysteps.timeseries.correlation.temporal_autocorrelation`` by the device version
+    (:mod:`pysteps_amd.timeseries.correlation`): the nowcast modules reach it through the module attribute, so steps,
+    sprog, sseps, blending.steps, pca_ens_kalman_filter and anvil then estimate their AR models from device sums;
+    inputs the device path declines run the reference's function with a ``RuntimeWarning``."""
+    return patch("correlation")
+
+
+def unpatch_correlation():
+    """Undo :func:`patch_correlation`."""
+    unpatch("correlation")
+
+
 def register_nowcasts():
     """Add ``"anvil_hip"`` (:func:`pysteps_amd.nowcasts.anvil.forecast`) and ``"lagrangian_probability_hip"``
     (:func:`pysteps_amd.nowcasts.lagrangian_probability.forecast`) to pysteps' nowcast table
@@ -332,7 +345,7 @@ def register_postprocessing(override=False):
 
 def register(override=False, patch_main_loop=False, fft=True, probmatching=False, autoregression=False,
              dilated_mask=False, fss=False, noise_stddev_adj=False, detscores=False, rapsd=False, probscores=False,
-             ensscores=False):
+             ensscores=False, correlation=False):
     """Register with an importable pysteps; raises ImportError if pysteps is absent.
 
     ``patch_main_loop=True`` also installs the device-resident generic nowcast loop
@@ -356,7 +369,9 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
     ``pysteps.verification.probscores`` accumulate the CRPS, reliability diagrams and ROC curves on the device
     (:func:`patch_probscores`; :func:`unpatch_probscores` undoes it).  ``ensscores=True`` makes
     ``pysteps.verification.ensscores`` compute ensemble skill and spread on the device (:func:`patch_ensscores`;
-    :func:`unpatch_ensscores` undoes it).
+    :func:`unpatch_ensscores` undoes it).  ``correlation=True`` makes
+    ``pysteps.timeseries.correlation.temporal_autocorrelation`` take its sums on the device (:func:`patch_correlation`;
+    :func:`unpatch_correlation` undoes it).
 
     ``"rainfarm_hip"`` joins ``pysteps.downscaling``'s method table (:func:`register_downscaling`), and
     ``"linear_blending_hip"`` and ``"salient_blending_hip"`` join ``pysteps.blending``'s (:func:`register_blending`)."""
@@ -389,7 +404,7 @@ def register(override=False, patch_main_loop=False, fft=True, probmatching=False
         added += register_spectral()
     for key, wanted in (("probmatching", probmatching), ("autoregression", autoregression), ("dilated_mask", dilated_mask),
                         ("fss", fss), ("noise_stddev_adj", noise_stddev_adj), ("detscores", detscores), ("rapsd", rapsd),
-                        ("probscores", probscores), ("ensscores", ensscores)):
+                        ("probscores", probscores), ("ensscores", ensscores), ("correlation", correlation)):
         if wanted:
             added += patch(key)
     if patch_main_loop:

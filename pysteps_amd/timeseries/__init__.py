@@ -1,3 +1,3 @@
-"""Mirrors of pysteps.timeseries operators that sit inside the nowcast member loops."""
+"""Mirrors of pysteps.timeseries operators that sit inside the nowcast member loops or in front of them."""
 
-from . import autoregression  # noqa: F401
+from . import autoregression, correlation  # noqa: F401
