@@ -1057,6 +1057,43 @@ int psh_rng_check(void *handle);
 int psh_rng_get_state(void *handle, uint32_t *keys_host, int *pos_host, int *has_gauss_host, double *gauss_host);
 int psh_rng_destroy(void *handle);
 
+/* ---- short-space Fourier (ssft / nested) noise (csrc/ssft.hip) -------------------------------------------------- *
+ * pysteps/noise/fftgenerators.py:442-852: the windowed filter bank of initialize_nonparam_2d_ssft_filter /
+ * initialize_nonparam_2d_nested_filter and the composite of generate_noise_2d_ssft_filter.  float64; filters are
+ * (m, n/2+1) half planes of the reference's real full-spectrum filters (Re(ifft2(fft2(N) F)) = irfft2 of the half of
+ * fft2(N) (F(k) + F(-k)) / 2); sizes as for the FFTs.  Every call is queued on the library stream and returns the same
+ * bits in every run.
+ * A window table (HOST memory, consumed before the call returns) holds 6 int64 per window: rows [i0, i1), columns
+ * [j0, j1), the element offset of the window's (i1 - i0, j1 - j0) mask tile in tiles_dev (negative: a mask of ones;
+ * tiles_dev may then be NULL) and the index of the filter plane the window writes or uses.  Rectangles outside the
+ * image, tiles outside the tiles_count elements of tiles_dev and planes outside nplanes are PSH_EINVAL.
+ *  psh_ssft_war_counts_dev     counts_dev[w] = number of (field, pixel) pairs of window w with field * mask > 0.01 over
+ *      the nr_fields planes of fields_dev (nr_fields, m, n): one rounded product, exact integers, all windows in one
+ *      launch (the plane column of the table is not read).
+ *  psh_ssft_local_filters_dev  per window: g = field * mask, mask zero outside the rectangle, prepared once more as
+ *      initialize_nonparam_2d_fft_filter prepares its input (fftgenerators.py:282-299: over the stack
+ *      g[g > g.min()] -= g[g > g.min()].min() - g.min(), then every field's minimum subtracted); the mean over the
+ *      fields of rfft2 of that; real and imaginary parts each standardised by their mean and population standard
+ *      deviation over the FULL plane where that deviation is > 0 (:316-321; the moments are read off the half plane,
+ *      a column with a mirror counting twice and the mirror's imaginary part negated; double-double sums in a fixed
+ *      order); np.abs; on the columns that are their own mirror images every pair (ky, -ky) takes its mean, so that
+ *      the plane is the fold of its own expansion.  Written to plane `plane` of planes_dev (nplanes, m, n/2+1).  taper_after != 0 (the global
+ *      filter; the window must be [0, m) x [0, n)): g = field and the tile multiplies the prepared field instead.
+ *  psh_ssft_merge_dev          plane = plane * weights + newfilter * (1 - weights) element by element, every
+ *      operation rounded (fftgenerators.py:708-725 on half planes).
+ *  psh_ssft_generate_dev       K white-noise planes (K, m, n) -> out_dev (K, m, n): rfft2 once per plane; per filter
+ *      plane in use irfft2(spectrum * plane) and out += that * mask inside every window of the plane, planes in the
+ *      order in which the table first names them (whatever their numbers) and a plane's windows in table order; out /= sM where sM_dev (m, n) > 0; (out - mean) / std
+ *      with the moments of psh_rainfarm_std_dev.  Member k's field holds the bits of a call with that plane alone. */
+int psh_ssft_war_counts_dev(const double *fields_dev, int nr_fields, int m, int n, const long long *wins_host, int nwin,
+                            const double *tiles_dev, size_t tiles_count, unsigned long long *counts_dev);
+int psh_ssft_local_filters_dev(const double *fields_dev, int nr_fields, int m, int n, const long long *wins_host, int nwin,
+                               const double *tiles_dev, size_t tiles_count, int taper_after, int nplanes, double *planes_dev);
+int psh_ssft_merge_dev(double *plane_dev, const double *weights_dev, const double *newfilter_dev, size_t count);
+int psh_ssft_generate_dev(const double *white_dev, int K, int m, int n, const double *planes_dev, int nplanes,
+                          const long long *wins_host, int nwin, const double *tiles_dev, size_t tiles_count,
+                          const double *sM_dev, double *out_dev);
+
 /* ---- multi-GPU: RCCL over xGMI, one rank (process) per GPU ------------------ *
  * The reference has no communication layer (single process, optional dask threads:
  * pysteps/nowcasts/utils.py:464-471); members / fields shard across GPUs with ONE

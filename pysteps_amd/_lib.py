@@ -180,6 +180,11 @@ SIGNATURES = {
     "psh_rng_check": (c_int, [c_void_p]),
     "psh_rng_get_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psh_rng_destroy": (c_int, [c_void_p]),
+    "psh_ssft_war_counts_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "psh_ssft_local_filters_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "psh_ssft_merge_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
+    "psh_ssft_generate_dev": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                      c_void_p, c_void_p]),
     "psh_lk_greedy_host": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p]),
     "psh_lk_order_host": (c_int, [c_void_p, c_int, c_float, c_double, c_int, c_int, c_double, c_int, c_void_p, c_void_p]),
     "psh_idw_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_int, c_double, c_double, c_double, c_void_p]),

@@ -11,6 +11,10 @@ grids take this path; ``use_full_fft`` filters, the spectral domain and other sh
 reference's own expression with the HIP FFT method object / numpy.
 
 The filter array is uploaded once and kept on the device while the filter dictionary's array lives.
+
+The localised generators of the same reference module - ``initialize_nonparam_2d_ssft_filter``,
+``initialize_nonparam_2d_nested_filter``, ``generate_noise_2d_ssft_filter`` - live in :mod:`pysteps_amd.noise.ssft`
+and are re-exported here.
 """
 
 import numpy as np
@@ -20,6 +24,9 @@ from .._reference import lookup
 from ..cascade.decomposition import _device_weights
 from ..device import DeviceArray
 from ..utils import fft as hip_fft
+# the short-space Fourier (ssft / nested) initialisers and their generator: noise/ssft.py
+from .ssft import (generate_noise_2d_ssft_filter, generate_noise_table,  # noqa: F401
+                   initialize_nonparam_2d_nested_filter, initialize_nonparam_2d_ssft_filter)
 
 
 def generate_noise_2d_fft_filter(F, randstate=None, seed=None, fft_method=None, domain="spatial"):

@@ -17,6 +17,8 @@ from ._reference import patch, restore, swap, unpatch
 FFT_NAME = "hip"
 CASCADE_NAME = "fft_hip"  # pysteps.cascade.get_method("fft_hip") -> (decomposition_fft, recompose_fft)
 NOISE_NAMES = {"parametric_hip": "parametric", "nonparametric_hip": "nonparametric"}
+# noise_method names whose initialiser AND generator are the device's (noise/ssft.py): name -> initialiser
+SSFT_NAMES = {"ssft_hip": "initialize_nonparam_2d_ssft_filter", "nested_hip": "initialize_nonparam_2d_nested_filter"}
 BPS_NAME = "bps_hip"  # vel_pert_method: the reference's generate_bps behind an initialiser that shares the unit fields
 EXTRAPOLATION_NAMES = ("semilagrangian_hip",)
 MOTION_NAMES = ("lk_hip", "lucaskanade_hip")
@@ -118,7 +120,9 @@ def register_spectral():
     """Insert the device cascade decomposition and noise generator into the reference's method tables
     (pysteps/cascade/interface.py:15-18 ``_cascade_methods``, pysteps/noise/interface.py:24-45
     ``_noise_methods``): ``decomp_method="fft_hip"`` and ``noise_method="nonparametric_hip"`` /
-    ``"parametric_hip"`` (the reference's filter initialisation paired with the HIP generator)."""
+    ``"parametric_hip"`` (the reference's filter initialisation paired with the HIP generator), and
+    ``noise_method="ssft_hip"`` / ``"nested_hip"`` (the device's local-filter initialisers with its composite
+    generator)."""
     import pysteps.cascade.interface as cas_if  # noqa: PLC0415
     import pysteps.noise.interface as noise_if  # noqa: PLC0415
 
@@ -131,6 +135,11 @@ def register_spectral():
     for name, stock in NOISE_NAMES.items():
         init = noise_if._noise_methods[stock][0]
         noise_if._noise_methods[name] = (init, generate_noise_2d_fft_filter)
+        added.append("noise:" + name)
+    from .noise import ssft  # noqa: PLC0415
+
+    for name, init in SSFT_NAMES.items():  # the stock "ssft" / "nested" stay the reference's
+        noise_if._noise_methods[name] = (getattr(ssft, init), ssft.generate_noise_2d_ssft_filter)
         added.append("noise:" + name)
     from .noise.motion import initialize_bps  # noqa: PLC0415
 
