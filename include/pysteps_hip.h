@@ -112,6 +112,54 @@ int psh_event_elapsed_ms(void *start, void *stop, float *ms); /* waits for stop 
  *   Synchronous. */
 int psh_db_transform_dev(const float *in_dev, float *out_dev, size_t n, double threshold,
                          double zerovalue, int inverse);
+/* Box-Cox, square-root and Z-R passes (pysteps/utils/transformation.py:27-147, 329-380; conversion.py:96, 262) on a
+ * float32 (f32 != 0) or float64 plane, in place allowed, queued on the library stream.  Every value is evaluated in
+ * double from the input and rounded once at the store; NaN stays NaN, log / sqrt / a fractional power of a negative
+ * number give NaN like NumPy.  Alignment and the two code paths are those of psh_db_transform_dev (16-byte vectors where
+ * both buffers allow it, else one element per thread with the same arithmetic).  `threshold` is the number NumPy would
+ * compare with, rounded by the caller as for psh_db_transform_dev; the comparisons run in double.
+ *   PSH_TRANSFORM_BOXCOX          p0 = Lambda: R < threshold ? zerovalue : (Lambda == 0 ? log R : (R^Lambda - 1) / Lambda)
+ *   PSH_TRANSFORM_BOXCOX_INVERSE  v = Lambda == 0 ? exp R : exp(log(Lambda R + 1) / Lambda) (Lambda R and + 1 rounded
+ *                                 separately); the STORED v < threshold ? zerovalue : v, threshold transformed back
+ *   PSH_TRANSFORM_SQRT / SQUARE   sqrt R / R R: correctly rounded in either dtype
+ *   PSH_TRANSFORM_Z_TO_RATE       (R / p0)^p1, p0 = zr_a, p1 = 1.0 / zr_b as the caller's Python forms it
+ *   PSH_TRANSFORM_RATE_TO_Z       p0 R^p1, p0 = zr_a, p1 = zr_b */
+enum {
+  PSH_TRANSFORM_BOXCOX = 0,
+  PSH_TRANSFORM_BOXCOX_INVERSE = 1,
+  PSH_TRANSFORM_SQRT = 2,
+  PSH_TRANSFORM_SQUARE = 3,
+  PSH_TRANSFORM_Z_TO_RATE = 4,
+  PSH_TRANSFORM_RATE_TO_Z = 5
+};
+int psh_field_transform_dev(const void *in_dev, void *out_dev, int f32, size_t n, int op, double p0, double p1,
+                            double threshold, double zerovalue);
+/* ---- normal-quantile transform (csrc/nqt.hip; pysteps/utils/transformation.py:237-326) ------------------------- *
+ * *_f32 != 0: float32, else float64.  At most 2^32 - 1 values (PSH_EUNSUPPORTED beyond).
+ *  psh_nqt_count_le_dev  count (n) uint32: for every pixel that is not NaN the number of values that are not NaN and
+ *      <= it, itself included (np.searchsorted(np.sort(x), x, side="right")); 0 for a NaN.  -0.0 counts as 0.0; a run
+ *      of ties may have any length.  sorted_dev (n elements of x's dtype) receives the *n_valid values that are not NaN
+ *      in ascending order, NaN behind them - the y table of the inverse.  *min_out / *max_out (host, may be NULL): the
+ *      first and the last of them, NaN if there is none.  stage_ms (NULL or 3 floats): device time of {keys and digit
+ *      histograms; sort passes; counts and the value table}.  Synchronous.
+ *  psh_nqt_forward_dev  out = NaN where x is NaN, 0 where x == zerovalue (compared in double), else
+ *      ndtri((count - a) / ((n_valid + 1) - 2 a)) in float64 (Cephes' three-branch approximation, as SciPy evaluates
+ *      it), stored as float64 or rounded once to float32.  *threshold_out (host, may be NULL): the smallest stored
+ *      result > 0, NaN if there is none.  Synchronous.
+ *  psh_nqt_table_dev  rqn[k] = ndtri(((k + 1) - a) / ((n_valid + 1) - 2 a)), k < n_valid: the x table of the inverse,
+ *      from the same device function.  Queued on the library stream.
+ *  psh_nqt_inverse_dev  scipy.interpolate.interp1d(rqn, sorted, bounds_error=False, fill_value=(sorted[0],
+ *      sorted[n_table - 1])) at every x that is not NaN, as SciPy evaluates it on float64 tables (np.interp): the
+ *      interval rqn[j] <= x < rqn[j + 1], sorted[j] itself at a knot, else slope * (x - x_lo) + y_lo in float64 with
+ *      each operation rounded on its own; sorted[0] below rqn[0], the last entry above the last.  n_table >= 2.  *min_out: the smallest stored result, *above_min_out: the smallest one above it
+ *      (host, may be NULL; NaN if there is none).  Synchronous. */
+int psh_nqt_count_le_dev(const void *x_dev, int f32, size_t n, unsigned *count_dev, void *sorted_dev, size_t *n_valid,
+                         double *min_out, double *max_out, float *stage_ms);
+int psh_nqt_forward_dev(const void *x_dev, int f32, const unsigned *count_dev, size_t n, size_t n_valid, double a,
+                        double zerovalue, void *out_dev, int out_f32, double *threshold_out);
+int psh_nqt_table_dev(size_t n_valid, double a, double *rqn_dev);
+int psh_nqt_inverse_dev(const void *x_dev, int f32, size_t n, const double *rqn_dev, const void *sorted_dev, int sorted_f32,
+                        size_t n_table, void *out_dev, int out_f32, double *min_out, double *above_min_out);
 /* float64 <-> float32 element conversion on the device (to_f64 != 0: float32 -> float64), so that
  * the float64 arrays pysteps works with cross the bus as they are instead of being narrowed /
  * widened by a host pass. */

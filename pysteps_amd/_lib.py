@@ -225,6 +225,14 @@ SIGNATURES = {
     "psh_lk_band_select_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p]),
     "psh_lk_track_pyr_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     "psh_db_transform_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_double, c_double, c_int]),
+    "psh_field_transform_dev": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_double, c_double, c_double, c_double]),
+    "psh_nqt_count_le_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, POINTER(c_size_t), POINTER(c_double),
+                                     POINTER(c_double), POINTER(c_float)]),
+    "psh_nqt_forward_dev": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_size_t, c_double, c_double, c_void_p, c_int,
+                                    POINTER(c_double)]),
+    "psh_nqt_table_dev": (c_int, [c_size_t, c_double, c_void_p]),
+    "psh_nqt_inverse_dev": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_int,
+                                    POINTER(c_double), POINTER(c_double)]),
     "psh_nonfinite_count_f64_dev": (c_int, [c_void_p, c_size_t, POINTER(c_double)]),
     "psh_field_stats_dev": (c_int, [c_void_p, c_size_t, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "psh_dense_lk_dev": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(LkParams), c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int)]),

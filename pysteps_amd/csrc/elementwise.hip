@@ -50,6 +50,78 @@ __global__ __launch_bounds__(256) void db_transform(const float *__restrict__ in
     out[i] = INVERSE ? from_db(in[i], thr, zerovalue) : to_db(in[i], thr, zerovalue);
 }
 
+// ---- Box-Cox, square root, Z-R laws (transformation.py:27-147, 329-380; conversion.py:96, 262) -------------------------
+// Every value is evaluated in double from the input and rounded once at the store; a `<` that decides on a computed value
+// (the inverse Box-Cox) compares the STORED value, widened, with the number NumPy would compare with.
+struct TransformArgs {
+  double p0, p1;  // Box-Cox: Lambda; Z-R: zr_a and the exponent (1 / zr_b towards the rain rate, zr_b towards Z)
+  double thr, zerovalue;
+};
+
+template <class T, int OP> __device__ __forceinline__ T transform_one(T x, const TransformArgs &a) {
+#pragma clang fp contract(off)  // Lambda * R + 1 is two roundings in the reference, and in both loops here
+  const double xd = static_cast<double>(x);
+  if (OP == PSH_TRANSFORM_BOXCOX) {
+    // zeros = R < threshold, decided on the input; log for Lambda == 0, else (R ** Lambda - 1) / Lambda
+    if (xd < a.thr) return static_cast<T>(a.zerovalue);
+    return static_cast<T>(a.p0 == 0.0 ? log(xd) : (pow(xd, a.p0) - 1.0) / a.p0);
+  }
+  if (OP == PSH_TRANSFORM_BOXCOX_INVERSE) {
+    const T v = static_cast<T>(a.p0 == 0.0 ? exp(xd) : exp(log(a.p0 * xd + 1.0) / a.p0));
+    return static_cast<double>(v) < a.thr ? static_cast<T>(a.zerovalue) : v;  // NaN compares false and stays
+  }
+  if (OP == PSH_TRANSFORM_SQRT) return static_cast<T>(sqrt(xd));
+  if (OP == PSH_TRANSFORM_SQUARE) return static_cast<T>(xd * xd);
+  if (OP == PSH_TRANSFORM_Z_TO_RATE) return static_cast<T>(pow(xd / a.p0, a.p1));
+  return static_cast<T>(a.p0 * pow(xd, a.p1));  // PSH_TRANSFORM_RATE_TO_Z
+}
+
+template <class T> struct Vec16;
+template <> struct Vec16<float> { using type = float4; };
+template <> struct Vec16<double> { using type = double2; };
+
+// VEC: 16-byte vectors and a scalar tail (both buffers 16-byte aligned); otherwise one element per thread, same arithmetic
+template <class T, int OP, bool VEC>
+__global__ __launch_bounds__(256) void transform_elements(const T *__restrict__ in, T *__restrict__ out, size_t n, TransformArgs a) {
+  using V = typename Vec16<T>::type;
+  constexpr size_t kPer = 16 / sizeof(T);
+  const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  const size_t first = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  const size_t nvec = VEC ? n / kPer : 0;
+  if (VEC) {
+    const V *inv = reinterpret_cast<const V *>(in);
+    V *outv = reinterpret_cast<V *>(out);
+    for (size_t i = first; i < nvec; i += stride) {
+      V v = inv[i];
+      T *e = reinterpret_cast<T *>(&v);
+#pragma unroll
+      for (size_t j = 0; j < kPer; ++j) e[j] = transform_one<T, OP>(e[j], a);
+      outv[i] = v;
+    }
+  }
+  for (size_t i = nvec * kPer + first; i < n; i += stride) out[i] = transform_one<T, OP>(in[i], a);
+}
+
+template <class T, int OP> void launch_transform(const T *in, T *out, size_t n, const TransformArgs &a, bool vec, dim3 grid, hipStream_t s) {
+  if (vec)
+    hipLaunchKernelGGL((transform_elements<T, OP, true>), grid, dim3(256), 0, s, in, out, n, a);
+  else
+    hipLaunchKernelGGL((transform_elements<T, OP, false>), grid, dim3(256), 0, s, in, out, n, a);
+}
+
+template <class T> int launch_transform_op(int op, const T *in, T *out, size_t n, const TransformArgs &a, bool vec, dim3 grid, hipStream_t s) {
+  switch (op) {
+    case PSH_TRANSFORM_BOXCOX: launch_transform<T, PSH_TRANSFORM_BOXCOX>(in, out, n, a, vec, grid, s); break;
+    case PSH_TRANSFORM_BOXCOX_INVERSE: launch_transform<T, PSH_TRANSFORM_BOXCOX_INVERSE>(in, out, n, a, vec, grid, s); break;
+    case PSH_TRANSFORM_SQRT: launch_transform<T, PSH_TRANSFORM_SQRT>(in, out, n, a, vec, grid, s); break;
+    case PSH_TRANSFORM_SQUARE: launch_transform<T, PSH_TRANSFORM_SQUARE>(in, out, n, a, vec, grid, s); break;
+    case PSH_TRANSFORM_Z_TO_RATE: launch_transform<T, PSH_TRANSFORM_Z_TO_RATE>(in, out, n, a, vec, grid, s); break;
+    case PSH_TRANSFORM_RATE_TO_Z: launch_transform<T, PSH_TRANSFORM_RATE_TO_Z>(in, out, n, a, vec, grid, s); break;
+    default: return fail(PSH_EINVAL, "field_transform: unknown operation %d", op);
+  }
+  return PSH_OK;
+}
+
 constexpr int kStatFields = 5;
 
 // float64 twin of field_stats (double partials): the host path checks float64 inputs BEFORE they are
@@ -188,6 +260,26 @@ extern "C" int psh_db_transform_dev(const float *in_dev, float *out_dev, size_t 
   auto kernel = inverse ? (vec ? psh::db_transform<true, true> : psh::db_transform<true, false>)
                         : (vec ? psh::db_transform<false, true> : psh::db_transform<false, false>);
   hipLaunchKernelGGL(kernel, grid, block, 0, c.stream, in_dev, out_dev, n, threshold, zv);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
+}
+
+extern "C" int psh_field_transform_dev(const void *in_dev, void *out_dev, int f32, size_t n, int op, double p0, double p1,
+                                       double threshold, double zerovalue) {
+  PSH_REQUIRE_INIT();
+  if (n == 0) return PSH_OK;
+  if (!in_dev || !out_dev) return psh::fail(PSH_EINVAL, "field_transform: NULL pointer");
+  const uintptr_t both = reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev);
+  if (both & (f32 ? 3 : 7)) return psh::fail(PSH_EINVAL, "field_transform: buffers must be aligned to their element");
+  const bool vec = (both & 15) == 0;
+  psh::Context &c = psh::ctx();
+  std::lock_guard<std::recursive_mutex> lock(c.mu);
+  PSH_HIP(hipSetDevice(c.device));
+  const dim3 grid(c.cu_count * 8);
+  const psh::TransformArgs a{p0, p1, threshold, zerovalue};
+  const int rc = f32 ? psh::launch_transform_op(op, static_cast<const float *>(in_dev), static_cast<float *>(out_dev), n, a, vec, grid, c.stream)
+                     : psh::launch_transform_op(op, static_cast<const double *>(in_dev), static_cast<double *>(out_dev), n, a, vec, grid, c.stream);
+  if (rc) return rc;
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }

@@ -1,7 +1,33 @@
-"""Sparse-vector utilities on the dense-LK path (mirrors of pysteps.utils.cleansing / interpolate)."""
+"""Sparse-vector utilities on the dense-LK path (mirrors of pysteps.utils.cleansing / interpolate), the transforms and
+the unit conversions."""
 
 from .cleansing import decluster, detect_outliers, detect_outliers_device  # noqa: F401
 from .interpolate import idwinterp2d, rbfinterp2d  # noqa: F401
-from .transformation import dB_transform  # noqa: F401,E402
+from .transformation import NQ_transform, boxcox_transform, dB_transform, sqrt_transform  # noqa: F401,E402
+from .conversion import to_raindepth, to_rainrate, to_reflectivity  # noqa: F401,E402
 from .check_norain import check_norain  # noqa: F401,E402
 from .spectral import RapsdAccumulator, rapsd, rapsd_counts, rapsd_table  # noqa: F401,E402
+
+# transformation and conversion names of pysteps/utils/interface.py, served from this package
+_METHODS = {
+    "mm/h": to_rainrate, "rainrate": to_rainrate,
+    "mm": to_raindepth, "raindepth": to_raindepth,
+    "dbz": to_reflectivity, "reflectivity": to_reflectivity,
+    "boxcox": boxcox_transform, "box-cox": boxcox_transform, "log": boxcox_transform,
+    "db": dB_transform, "decibel": dB_transform,
+    "nqt": NQ_transform,
+    "sqrt": sqrt_transform,
+}
+
+
+def get_method(name, **kwargs):
+    """``pysteps.utils.get_method``: the transformation and conversion methods come from this package, every other name
+    from the reference's table.  ``None`` is "none", names are matched in lower case."""
+    if name is None:
+        name = "none"
+    name = name.lower()
+    if name in _METHODS:
+        return _METHODS[name]
+    import importlib
+
+    return importlib.import_module("pysteps.utils").get_method(name, **kwargs)
