@@ -19,6 +19,9 @@
  *    as in semilagrangian.py:44-46.
  *  - displacement is (2,m,n) float64 on both sides of the boundary, the dtype
  *    the reference returns (semilagrangian.py:201,264-266).
+ *  - threads: calls from several threads are serialised by the library lock, and
+ *    psh_shutdown may race with a call only in the sense that the call then
+ *    returns PSH_ENOTINIT.
  */
 #ifndef PYSTEPS_HIP_H
 #define PYSTEPS_HIP_H

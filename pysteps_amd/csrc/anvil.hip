@@ -344,29 +344,23 @@ using psh::fail;
 extern "C" int psh_anvil_gauss_dev(const double *in0_dev, const double *in1_dev, const double *in2_dev, int recipe, int m, int n,
                                    const double *weights_host, int radius, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = check_shape("anvil_gauss", m, n)) return rc;
   if (!weights_host || !out_dev) return fail(PSH_EINVAL, "anvil_gauss: NULL pointer");
   if (radius < 0 || radius > kAnvilMaxRadius) return fail(PSH_EUNSUPPORTED, "anvil_gauss: kernel radius %d (0..%d)", radius, kAnvilMaxRadius);
   const bool ok = (recipe == kPlain && in0_dev && (in1_dev || !in2_dev)) || (recipe == kCorr && in0_dev && in1_dev) ||
                   (recipe == kRvil && in0_dev && in1_dev && in2_dev) || (recipe == kOnes && !in0_dev && !in1_dev && !in2_dev);
   if (!ok) return fail(PSH_EINVAL, "anvil_gauss: recipe %d does not take these inputs", recipe);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   return gauss(in0_dev, in1_dev, in2_dev, recipe, m, n, weights_host, radius, out_dev, c.stream);
 }
 
 extern "C" int psh_anvil_phi_dev(const double *nwin_dev, const double *fields_dev, int ar_order, int m, int n, double *phi_dev,
                                  double *gamma_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = check_shape("anvil_phi", m, n)) return rc;
   if (!nwin_dev || !fields_dev || !phi_dev) return fail(PSH_EINVAL, "anvil_phi: NULL pointer");
   if (ar_order != 1 && ar_order != 2) return fail(PSH_EUNSUPPORTED, "anvil_phi: ar_order %d (1 or 2)", ar_order);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t count = static_cast<size_t>(m) * n;
   hipLaunchKernelGGL(anvil_phi, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, nwin_dev, fields_dev, ar_order, count, phi_dev,
                      gamma_dev);
@@ -377,13 +371,10 @@ extern "C" int psh_anvil_phi_dev(const double *nwin_dev, const double *fields_de
 extern "C" int psh_anvil_rvil_dev(const double *vil_dev, const double *rainrate_dev, int m, int n, const double *weights_host,
                                   int radius, double *a_dev, double *b_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = check_shape("anvil_rvil", m, n)) return rc;
   if (!vil_dev || !rainrate_dev || !weights_host || !a_dev || !b_dev) return fail(PSH_EINVAL, "anvil_rvil: NULL pointer");
   if (radius < 0 || radius > kAnvilMaxRadius) return fail(PSH_EUNSUPPORTED, "anvil_rvil: kernel radius %d (0..%d)", radius, kAnvilMaxRadius);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t count = static_cast<size_t>(m) * n;
   psh::Scratch blk;
   if (int rc = blk.alloc(8 * count * sizeof(double))) return rc;
@@ -400,13 +391,10 @@ extern "C" int psh_anvil_rvil_dev(const double *vil_dev, const double *rainrate_
 extern "C" int psh_anvil_masks_dev(const double *frames_dev, int K, int m, int n, double *zeroed_dev, unsigned char *mask_dev,
                                    unsigned char *rr_mask_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = check_shape("anvil_masks", m, n)) return rc;
   if (!frames_dev || !zeroed_dev || !mask_dev) return fail(PSH_EINVAL, "anvil_masks: NULL pointer");
   if (K < 1 || K > 64) return fail(PSH_EINVAL, "anvil_masks: %d frames", K);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t count = static_cast<size_t>(m) * n;
   hipLaunchKernelGGL(anvil_masks, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, frames_dev, K, count, zeroed_dev, mask_dev,
                      rr_mask_dev);
@@ -416,12 +404,9 @@ extern "C" int psh_anvil_masks_dev(const double *frames_dev, int K, int m, int n
 
 extern "C" int psh_anvil_diff_dev(const double *older_dev, const double *newer_dev, size_t count, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!older_dev || !newer_dev || !out_dev) return fail(PSH_EINVAL, "anvil_diff: NULL pointer");
   if (count == 0) return PSH_OK;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(anvil_diff, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, older_dev, newer_dev, count, out_dev);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
@@ -431,16 +416,13 @@ extern "C" int psh_anvil_update_dev(double *ring_dev, const double *phi_dev, int
                                     const unsigned char *mask_dev, const unsigned char *rr_mask_dev, const double *a_dev,
                                     const double *b_dev, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = check_shape("anvil_update", m, n)) return rc;
   if (!ring_dev || !phi_dev || !mask_dev || !out_dev || (a_dev == nullptr) != (b_dev == nullptr))
     return fail(PSH_EINVAL, "anvil_update: NULL pointer");
   if (n_levels < 1 || n_levels > 64) return fail(PSH_EINVAL, "anvil_update: %d levels", n_levels);
   if (p != 2 && p != 3) return fail(PSH_EUNSUPPORTED, "anvil_update: %d AR terms (2 or 3)", p);
   if (head < 0 || head >= p) return fail(PSH_EINVAL, "anvil_update: ring head %d of %d slots", head, p);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t count = static_cast<size_t>(m) * n;
   if (p == 2)
     hipLaunchKernelGGL(anvil_update<2>, dim3(grid_for(count)), dim3(kAnvilThreads), 0, c.stream, ring_dev, phi_dev, n_levels, count, head,

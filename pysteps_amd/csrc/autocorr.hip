@@ -288,7 +288,7 @@ using psh::fail;
 extern "C" int psh_autocorr_sums_dev(const void *stack_dev, int is_f64, int nlevels, int nframes, size_t npix,
                                      const unsigned char *mask_dev, int d, double *sums_dev, unsigned long long *count_dev,
                                      unsigned long long *nonfinite_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!stack_dev || !sums_dev || !count_dev || !nonfinite_dev) return fail(PSH_EINVAL, "autocorr_sums: NULL pointer");
   if (d != 0 && d != 1) return fail(PSH_EINVAL, "autocorr_sums: d must be 0 or 1");
   if (nlevels < 1 || nlevels > 65535 || npix == 0) return fail(PSH_EINVAL, "autocorr_sums: 1..65535 levels, not empty");
@@ -297,9 +297,6 @@ extern "C" int psh_autocorr_sums_dev(const void *stack_dev, int is_f64, int nlev
   if (K > psh::kAcMaxLags) return fail(PSH_EUNSUPPORTED, "autocorr_sums: at most %d lags", psh::kAcMaxLags);
   const size_t item = is_f64 ? sizeof(double) : sizeof(float);
   if (reinterpret_cast<uintptr_t>(stack_dev) % item) return fail(PSH_EINVAL, "autocorr_sums: misaligned stack");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nsums = 2 + 3 * K;
   const unsigned blocks = psh::ac_blocks((npix + 1) / 2);
   psh::Scratch partial;
@@ -327,7 +324,7 @@ extern "C" int psh_autocorr_sums_dev(const void *stack_dev, int is_f64, int nlev
 
 extern "C" int psh_autocorr_spectral_sums_dev(const void *spec_dev, int nlevels, int nframes, int m, int nc, int n, int full_fft,
                                               int d, double *sums_dev, unsigned long long *nonfinite_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!spec_dev || !sums_dev || !nonfinite_dev) return fail(PSH_EINVAL, "autocorr_spectral_sums: NULL pointer");
   if (d != 0 && d != 1) return fail(PSH_EINVAL, "autocorr_spectral_sums: d must be 0 or 1");
   if (nlevels < 1 || nlevels > 65535 || m < 1 || n < 1) return fail(PSH_EINVAL, "autocorr_spectral_sums: invalid shape");
@@ -336,9 +333,6 @@ extern "C" int psh_autocorr_spectral_sums_dev(const void *spec_dev, int nlevels,
   if (K < 1) return fail(PSH_EINVAL, "autocorr_spectral_sums: at least %d frames", 2 + d);
   if (K > psh::kAcMaxLags) return fail(PSH_EUNSUPPORTED, "autocorr_spectral_sums: at most %d lags", psh::kAcMaxLags);
   if (reinterpret_cast<uintptr_t>(spec_dev) % sizeof(double2)) return fail(PSH_EINVAL, "autocorr_spectral_sums: misaligned spectra");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nsums = 1 + 2 * K;
   const size_t plane = static_cast<size_t>(m) * nc;
   const unsigned blocks = psh::ac_blocks(plane);
@@ -363,12 +357,9 @@ extern "C" int psh_autocorr_spectral_sums_dev(const void *spec_dev, int nlevels,
 
 extern "C" int psh_autocorr_window_prepare_dev(const double *stack_dev, int nframes, size_t npix, const unsigned char *mask_dev, int d,
                                                double *out_dev, unsigned long long *nonfinite_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!stack_dev || !out_dev || !nonfinite_dev) return fail(PSH_EINVAL, "autocorr_window_prepare: NULL pointer");
   if ((d != 0 && d != 1) || nframes - d < 2 || npix == 0) return fail(PSH_EINVAL, "autocorr_window_prepare: d 0 or 1, two planes after it");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemsetAsync(nonfinite_dev, 0, sizeof(unsigned long long), c.stream));
   hipLaunchKernelGGL(psh::window_prepare, dim3(static_cast<unsigned>(std::min<size_t>((npix + psh::kAcThreads - 1) / psh::kAcThreads, 4096))), dim3(psh::kAcThreads), 0,
                      c.stream, stack_dev, nframes, d, npix, mask_dev, out_dev, nonfinite_dev);
@@ -378,12 +369,9 @@ extern "C" int psh_autocorr_window_prepare_dev(const double *stack_dev, int nfra
 
 extern "C" int psh_window_corrcoef_dev(const double *n_dev, const double *sx_dev, const double *sy_dev, const double *ssx_dev,
                                        const double *ssy_dev, const double *sxy_dev, double factor, size_t count, double *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!n_dev || !sx_dev || !sy_dev || !ssx_dev || !ssy_dev || !sxy_dev || !out_dev) return fail(PSH_EINVAL, "window_corrcoef: NULL pointer");
   if (count == 0) return fail(PSH_EINVAL, "window_corrcoef: empty planes");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::window_corrcoef, dim3(static_cast<unsigned>(std::min<size_t>((count + psh::kAcThreads - 1) / psh::kAcThreads, 4096))), dim3(psh::kAcThreads),
                      0, c.stream, n_dev, sx_dev, sy_dev, ssx_dev, ssy_dev, sxy_dev, factor, count, out_dev);
   PSH_HIP(hipGetLastError());

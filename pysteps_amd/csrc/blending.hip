@@ -458,14 +458,11 @@ using psh::fail;
 extern "C" int psh_blend_linear_dev(const void *nowcast_dev, int nowcast_f32, const void *nwp_dev, int nwp_f32,
                                     const long long *offsets_dev, int K, size_t plane, int mode, double weight_nwp,
                                     double weight_nowcast, int fill_nwp, void *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = psh::check_planes("blend_linear", nwp_dev, out_dev, offsets_dev, K, plane)) return rc;
   if (mode < 0 || mode > 2) return fail(PSH_EINVAL, "blend_linear: mode must be 0, 1 or 2");
   if (mode != 1 && !nowcast_dev) return fail(PSH_EINVAL, "blend_linear: the nowcast is needed");
   if ((mode != 0 || fill_nwp) && !nwp_dev) return fail(PSH_EINVAL, "blend_linear: the NWP is needed");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
 #define PSH_BLEND_LINEAR(TN, TW)                                                                                          \
   return psh::linear_impl(psh::Planes<TN, TW>{static_cast<const TN *>(nowcast_dev), static_cast<const TW *>(nwp_dev),   \
                                               static_cast<TW *>(out_dev), offsets_dev, K, plane, fill_nwp},               \
@@ -481,13 +478,10 @@ extern "C" int psh_blend_salient_dev(const void *nowcast_dev, int nowcast_f32, c
                                      const long long *offsets_dev, int K, size_t plane, double weight, double one_minus_weight,
                                      double weight_sq, double one_minus_weight_sq, int fill_nwp, void *out_dev, int *status,
                                      float *stage_ms) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = psh::check_planes("blend_salient", nwp_dev, out_dev, offsets_dev, K, plane)) return rc;
   if (!nowcast_dev || !nwp_dev || !status) return fail(PSH_EINVAL, "blend_salient: NULL pointer");
   if (plane > psh::kMaxKeys / static_cast<size_t>(K)) return fail(PSH_EUNSUPPORTED, "blend_salient: more than 2^31 values to rank");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
 #define PSH_BLEND_SALIENT(TN, TW)                                                                                          \
   return psh::salient_impl(psh::Planes<TN, TW>{static_cast<const TN *>(nowcast_dev), static_cast<const TW *>(nwp_dev),   \
                                                static_cast<TW *>(out_dev), offsets_dev, K, plane, fill_nwp},               \
@@ -500,35 +494,26 @@ extern "C" int psh_blend_salient_dev(const void *nowcast_dev, int nowcast_f32, c
 }
 
 extern "C" int psh_blend_dense_rank_dev(const void *x_dev, int f32, size_t n, unsigned *rank_dev, unsigned *distinct) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!x_dev || !rank_dev || !distinct) return fail(PSH_EINVAL, "blend_dense_rank: NULL pointer");
   if (n == 0) return fail(PSH_EINVAL, "blend_dense_rank: nothing to rank");
   if (n > psh::kMaxKeys) return fail(PSH_EUNSUPPORTED, "blend_dense_rank: more than 2^31 values to rank");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   return psh::with_real(x_dev, !f32, [&](auto *x) { return psh::rank_impl(x, n, rank_dev, distinct, c.stream); });
 }
 
 extern "C" int psh_blend_db_inverse_f64_dev(const double *in_dev, double *out_dev, size_t n, double threshold_db, double zerovalue) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n == 0) return PSH_OK;
   if (!in_dev || !out_dev) return fail(PSH_EINVAL, "blend_db_inverse_f64: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::db_inverse_f64, dim3(psh::grid_x(n)), dim3(psh::kThreads), 0, c.stream, in_dev, out_dev, n, threshold_db, zerovalue);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
 extern "C" int psh_blend_scale_dev(const void *in_dev, void *out_dev, int f32, size_t n, double divisor, double factor) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n == 0) return PSH_OK;
   if (!in_dev || !out_dev) return fail(PSH_EINVAL, "blend_scale: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const dim3 grid(psh::grid_x(n)), block(psh::kThreads);
   if (f32)
     hipLaunchKernelGGL(psh::scale_elements<float>, grid, block, 0, c.stream, static_cast<const float *>(in_dev), static_cast<float *>(out_dev),

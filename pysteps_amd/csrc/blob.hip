@@ -268,7 +268,7 @@ using psh::fail;
 
 extern "C" int psh_blob_cube_dev(const void *image_dev, int image_is_f32, int m, int n, int method, const double *sigmas_host,
                                  int nsig, const int *radius_host, const double *weights_host, double *cube_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!image_dev || !sigmas_host || !radius_host || !weights_host || !cube_dev) return fail(PSH_EINVAL, "blob_cube: NULL pointer");
   if (m <= 0 || n <= 0 || static_cast<size_t>(m) * n > (size_t(1) << 30)) return fail(PSH_EINVAL, "blob_cube: invalid shape (%d,%d)", m, n);
   if (method != 0 && method != 1) return fail(PSH_EINVAL, "blob_cube: method 0 (LoG) or 1 (DoG)");
@@ -276,9 +276,6 @@ extern "C" int psh_blob_cube_dev(const void *image_dev, int image_is_f32, int m,
   for (int k = 0; k < nsig; ++k)
     if (radius_host[k] < 0 || radius_host[k] > psh::kBlobMaxRadius)
       return fail(PSH_EUNSUPPORTED, "blob_cube: kernel radius %d (0..%d)", radius_host[k], psh::kBlobMaxRadius);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   return psh::with_real(image_dev, !image_is_f32, [&](auto *image) {
     return psh::blob_cube(image, m, n, method, sigmas_host, nsig, radius_host, weights_host, cube_dev, c.stream);
   });
@@ -287,12 +284,9 @@ extern "C" int psh_blob_cube_dev(const void *image_dev, int image_is_f32, int m,
 extern "C" int psh_blob_peaks_dev(const double *cube_dev, int K, int m, int n, double threshold, int capacity, int *coords_host,
                                   double *values_host, int *count_host) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!cube_dev || !coords_host || !values_host || !count_host) return fail(PSH_EINVAL, "blob_peaks: NULL pointer");
   if (K < 1 || m <= 0 || n <= 0 || capacity < 1) return fail(PSH_EINVAL, "blob_peaks: invalid shape or capacity");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n, total = plane * K;
   const size_t cbytes = (total * sizeof(double) + 255) & ~static_cast<size_t>(255);
   const size_t lbytes = (static_cast<size_t>(capacity) * 3 * sizeof(int) + 255) & ~static_cast<size_t>(255);
@@ -337,15 +331,12 @@ extern "C" int psh_blob_peaks_dev(const double *cube_dev, int K, int m, int n, d
 
 extern "C" int psh_blob_gather_dev(const double *plane_dev, int m, int n, const int *yx_host, int count, double *values_host) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!plane_dev || !yx_host || !values_host) return fail(PSH_EINVAL, "blob_gather: NULL pointer");
   if (count <= 0) return PSH_OK;
   for (int i = 0; i < count; ++i)
     if (yx_host[2 * i] < 0 || yx_host[2 * i] >= m || yx_host[2 * i + 1] < 0 || yx_host[2 * i + 1] >= n)
       return fail(PSH_EINVAL, "blob_gather: pixel (%d,%d) outside the (%d,%d) plane", yx_host[2 * i], yx_host[2 * i + 1], m, n);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t ibytes = (static_cast<size_t>(count) * 2 * sizeof(int) + 255) & ~static_cast<size_t>(255);
   psh::Scratch blk;
   if (int rc = blk.alloc(ibytes + static_cast<size_t>(count) * sizeof(double))) return rc;

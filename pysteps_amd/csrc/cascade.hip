@@ -173,7 +173,7 @@ static int cascade_decompose_run(const double *field_dev, const double *weights_
                                  int normalize, int subtract_mean, double *levels_dev, double *means_host,
                                  double *stds_host, double *field_mean_host, double *stats_out_dev,
                                  bool levels_only = false) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || !weights_dev || !levels_dev) return fail(PSH_EINVAL, "cascade_decompose: NULL pointer");
   if ((means_host == nullptr) != (stds_host == nullptr))
     return fail(PSH_EINVAL, "cascade_decompose: means and stds go together");
@@ -182,9 +182,6 @@ static int cascade_decompose_run(const double *field_dev, const double *weights_
   if (nlevels < 1 || nlevels > 64) return fail(PSH_EINVAL, "cascade_decompose: 1..64 cascade levels");
   if (!psh::fft_shape_supported(m, n))
     return fail(PSH_EUNSUPPORTED, "cascade_decompose: (%d,%d) - sides: powers of two up to 8192 or any length up to 4096", m, n);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n, nc = static_cast<size_t>(n / 2 + 1);
   const size_t spec_bytes = static_cast<size_t>(m) * nc * sizeof(double2);
   psh::Scratch blk;
@@ -252,14 +249,11 @@ extern "C" int psh_cascade_decompose_levels_dev(const double *field_dev, const d
 
 extern "C" int psh_cascade_recompose_dev(const double *levels_dev, int nlevels, int m, int n, const double *means_host,
                                          const double *stds_host, double field_mean, double *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!levels_dev || !out_dev) return fail(PSH_EINVAL, "cascade_recompose: NULL pointer");
   if (nlevels < 1 || nlevels > 64 || m <= 0 || n <= 0) return fail(PSH_EINVAL, "cascade_recompose: invalid shape");
   if ((means_host == nullptr) != (stds_host == nullptr))
     return fail(PSH_EINVAL, "cascade_recompose: means and stds go together");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const double *musigma = nullptr;
   if (means_host) {  // per-call constants through the pinned slot ring (floats: two per double)
     float *h = nullptr;
@@ -281,13 +275,10 @@ extern "C" int psh_cascade_recompose_dev(const double *levels_dev, int nlevels, 
 }
 
 extern "C" int psh_noise_filter_dev(const double *white_dev, const double *filter_dev, int m, int n, double *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!white_dev || !filter_dev || !out_dev) return fail(PSH_EINVAL, "noise_filter: NULL pointer");
   if (!psh::fft_shape_supported(m, n))
     return fail(PSH_EUNSUPPORTED, "noise_filter: (%d,%d) - sides: powers of two up to 8192 or any length up to 4096", m, n);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n;
   const size_t spec_bytes = static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2);
   psh::Scratch blk;
@@ -305,15 +296,12 @@ extern "C" int psh_noise_filter_dev(const double *white_dev, const double *filte
 
 extern "C" int psh_ar_iterate_dev(const double *x_dev, int nt, size_t plane, const double *phi_host, int p,
                                   const double *eps_dev, double *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!x_dev || !phi_host || !out_dev) return fail(PSH_EINVAL, "ar_iterate: NULL pointer");
   if (plane == 0 || nt < 1) return fail(PSH_EINVAL, "ar_iterate: empty series");
   if (p < 1 || p > psh::kArMaxOrder) return fail(PSH_EUNSUPPORTED, "ar_iterate: AR order 1..%d", psh::kArMaxOrder);
   if (nt < p)  // autoregression.py:1041-1045
     return fail(PSH_EINVAL, "dimension mismatch between x and phi: x.shape[0]=%d, len(phi)=%d", nt, p + 1);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::ArPhi a;
   for (int j = 0; j <= p; ++j) a.phi[j] = phi_host[j];
   a.p = p;

@@ -95,14 +95,11 @@ int psh_comm_unique_id(void *id_out) {
 }
 
 int psh_comm_init(const void *id, int nranks, int rank) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!id) return fail(PSH_EINVAL, "psh_comm_init: NULL id");
   if (nranks < 1 || rank < 0 || rank >= nranks)
     return fail(PSH_EINVAL, "psh_comm_init: bad rank %d of %d", rank, nranks);
   if (int rc = psh::load_rccl()) return rc;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (rccl().comm) return fail(PSH_EINVAL, "psh_comm_init: communicator already initialised");
   psh::UniqueId uid;
   std::memcpy(&uid, id, sizeof(uid));
@@ -115,13 +112,10 @@ int psh_comm_init(const void *id, int nranks, int rank) {
 }
 
 int psh_comm_broadcast(void *buf_dev, size_t nbytes, int root) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!rccl().comm) return fail(PSH_ECOMM, "psh_comm_broadcast: communicator not initialised");
   if (!buf_dev && nbytes) return fail(PSH_EINVAL, "psh_comm_broadcast: NULL buffer");
   if (root < 0 || root >= rccl().nranks) return fail(PSH_EINVAL, "psh_comm_broadcast: bad root %d", root);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (nbytes == 0) return PSH_OK;
   // one large in-place message: xGMI is point-to-point (per-link bound), so the
   // fields travel as a single pipelined broadcast instead of many small ones
@@ -131,12 +125,9 @@ int psh_comm_broadcast(void *buf_dev, size_t nbytes, int root) {
 }
 
 int psh_comm_allgather(const void *send_dev, void *recv_dev, size_t nbytes_per_rank) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!rccl().comm) return fail(PSH_ECOMM, "psh_comm_allgather: communicator not initialised");
   if ((!send_dev || !recv_dev) && nbytes_per_rank) return fail(PSH_EINVAL, "psh_comm_allgather: NULL buffer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (nbytes_per_rank == 0) return PSH_OK;
   if (int rc = rccl().all_gather(send_dev, recv_dev, nbytes_per_rank, psh::kNcclUint8, rccl().comm, c.stream))
     return psh::rccl_fail("ncclAllGather", rc);
@@ -144,14 +135,11 @@ int psh_comm_allgather(const void *send_dev, void *recv_dev, size_t nbytes_per_r
 }
 
 int psh_comm_allreduce_f32(float *buf_dev, size_t count, int op) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!rccl().comm) return fail(PSH_ECOMM, "psh_comm_allreduce: communicator not initialised");
   if (!buf_dev && count) return fail(PSH_EINVAL, "psh_comm_allreduce: NULL buffer");
   const int red = op == PSH_COMM_MIN ? psh::kNcclMin : op == PSH_COMM_MAX ? psh::kNcclMax : op == PSH_COMM_SUM ? psh::kNcclSum : -1;
   if (red < 0) return fail(PSH_EINVAL, "psh_comm_allreduce: unknown reduction %d", op);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (count == 0) return PSH_OK;
   if (int rc = rccl().all_reduce(buf_dev, buf_dev, count, psh::kNcclFloat32, red, rccl().comm, c.stream))
     return psh::rccl_fail("ncclAllReduce", rc);
@@ -159,11 +147,11 @@ int psh_comm_allreduce_f32(float *buf_dev, size_t count, int op) {
 }
 
 int psh_comm_destroy(void) {
+  psh::Context &c = psh::ctx();  // not through the guard: a communicator is closed whether the library is up or not
+  psh::Lock lock(c.mu);
   if (!rccl().comm) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
   if (c.ready) {
-    (void)hipSetDevice(c.device);
+    (void)psh::bind_device(c.device);
     (void)hipStreamSynchronize(c.stream);
   }
   const int rc = rccl().comm_destroy(rccl().comm);

@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "../../include/pysteps_hip.h"
+#include "entry.h"
 #include "scratch.h"
 
 // Device-side assertions of the debug build (python -m pysteps_amd.build --debug: -O1 -g -DPSH_DEBUG): compiled out
@@ -75,12 +76,6 @@ int const_slot(float **host, const float **dev);
     if (_e != hipSuccess)                                                        \
       return ::psh::fail(PSH_EHIP, "%s failed: %s (%s:%d)", #expr,               \
                          hipGetErrorString(_e), __FILE__, __LINE__);             \
-  } while (0)
-
-#define PSH_REQUIRE_INIT()                                                       \
-  do {                                                                           \
-    if (!::psh::ctx().ready)                                                     \
-      return ::psh::fail(PSH_ENOTINIT, "psh_init() has not been called");        \
   } while (0)
 
 // Element-type dispatch of the entry points that take `const void *` plus an "is float64" flag: f is called with the
@@ -184,6 +179,7 @@ struct IdwArgs {
   const IdwDyn *dyn = nullptr;
 };
 hipError_t launch_idw(const IdwArgs &a, hipStream_t stream);
+// (lock held by the caller)
 int idw_resident(const float *xy_dev, const float *values_dev, int capacity, const IdwDyn *dyn_dev, int m, int n,
                  int k, double power, double dist_offset, float *out_dev, float *out_uv_dev = nullptr);
 size_t idw_scratch_bytes(int m, int n);
@@ -195,7 +191,7 @@ hipError_t launch_outliers_pooled(const double *xy_dev, const double *uv_dev, co
 // tracker with device-side pooling of the successful vectors (lk.hip); asynchronous.  The points
 // come either from the host (staged in a pinned slot that stays valid until the stream has
 // consumed it) or from device memory together with their count (points_dev, npts_dev; npts is
-// then the capacity).
+// then the capacity).  Lock held by the caller.
 int lk_track_pool(void *pyramid_handle, const float *points_host, const float *points_dev, const int *npts_dev,
                   int npts, int max_count, double epsilon, double min_eig_threshold, double *pool_xy_dev,
                   double *pool_uv_dev, int *pool_count_dev, int pool_capacity);
@@ -206,6 +202,7 @@ int lk_track_pool(void *pyramid_handle, const float *points_host, const float *p
 // is a single workgroup, so independent work forked there (side_begin) runs beside it.
 // walk_stats_host (may be NULL, else int[13]): waits for the stream and returns {chunks, candidates, rounds}
 // of the walk and the microseconds it spent {loading, sorting, on coordinates, in block tests, in batches, in all}.
+// Lock held by the caller.
 int lk_corners_resident(const unsigned char *feature_u8_dev, const float *clean_dev, float *stats_dev, int m, int n,
                         int block_size, int buffer_mask, double quality_level, double min_distance, int max_corners,
                         float *points_dev, int *npoints_dev, int (*before_walk)(void *) = nullptr,
@@ -227,8 +224,7 @@ size_t lk_keepbits_bytes(int m, int n);
 // the corner passes of the SAME frame fold their minima / maxima into instead of going through a
 // single-workgroup finishing kernel; a caller that passes none gets them cleared by a fill launch
 size_t lk_slot_bytes();
-int lk_pyramids_beside(const unsigned char *prev_u8_dev, const unsigned char *next_u8_dev, int m, int n, int win_w,
-                       int win_h, int max_level, void **handle_out);
+// (lock held by the caller)
 int lk_pyramids_on_side(hipStream_t side, void *block, size_t block_bytes, const unsigned char *prev_u8_dev,
                         const unsigned char *next_u8_dev, int m, int n, int win_w, int win_h, int max_level,
                         void **handle_out);

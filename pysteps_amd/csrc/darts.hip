@@ -280,11 +280,8 @@ GramArgs gram_args(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx,
 
 extern "C" int psh_darts_nonfinite_dev(const void *frames_dev, int f32, size_t count, int *flag_host) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frames_dev || !flag_host) return fail(PSH_EINVAL, "darts_nonfinite: NULL pointer");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc(sizeof(int))) return rc;
   int *flag = blk.as<int>();
@@ -302,7 +299,7 @@ extern "C" int psh_darts_nonfinite_dev(const void *frames_dev, int f32, size_t c
 
 extern "C" int psh_darts_band_dev(const void *frames_dev, int f32, int T, int m, int n, int ky, int kx, int nt, void *cube_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frames_dev || !cube_dev) return fail(PSH_EINVAL, "darts_band: NULL pointer");
   if (T < 1 || T > kDartsMaxFrames) return fail(PSH_EUNSUPPORTED, "darts_band: %d frames (1..%d)", T, kDartsMaxFrames);
   if (m < 2 || n < 2) return fail(PSH_EINVAL, "darts_band: shape %d x %d", m, n);
@@ -310,9 +307,6 @@ extern "C" int psh_darts_band_dev(const void *frames_dev, int f32, int T, int m,
     return fail(PSH_EINVAL, "darts_band: band %d x %d x %d outside %d x %d x %d", ky, kx, nt, m, n, T);
   const int by = 2 * ky + 1, bx = 2 * kx + 1;
   if (static_cast<long long>(by) * bx > (1LL << 26)) return fail(PSH_EUNSUPPORTED, "darts_band: band too large");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n, nc = static_cast<size_t>(n / 2 + 1);
   const size_t P = static_cast<size_t>(by) * bx;
   const size_t spec_bytes = static_cast<size_t>(m) * nc * sizeof(double2);
@@ -350,7 +344,7 @@ extern "C" int psh_darts_band_dev(const void *frames_dev, int f32, int T, int m,
 
 extern "C" int psh_darts_gram_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx, double cy, double cx, void *out_host) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!cube_dev || !out_host) return fail(PSH_EINVAL, "darts_gram: NULL pointer");
   if (int rc = check_gram("darts_gram", Nt, Ny, Nx, My, Mx)) return rc;
   const GramArgs a = gram_args(cube_dev, Nt, Ny, Nx, My, Mx, cy, cx);
@@ -359,9 +353,6 @@ extern "C" int psh_darts_gram_dev(const void *cube_dev, int Nt, int Ny, int Nx, 
   const int groups = (nout + per_group - 1) / per_group;
   const int nblocks = std::min(kGramBlocks, (a.rows + kGramRows - 1) / kGramRows);
   const int rows_per_block = (a.rows + nblocks - 1) / nblocks;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc((static_cast<size_t>(nblocks) + 1) * nout * sizeof(double2))) return rc;
   double2 *slab = blk.as<double2>(), *out = slab + static_cast<size_t>(nblocks) * nout;
@@ -378,13 +369,10 @@ extern "C" int psh_darts_gram_dev(const void *cube_dev, int Nt, int Ny, int Nx, 
 extern "C" int psh_darts_rows_dev(const void *cube_dev, int Nt, int Ny, int Nx, int My, int Mx, double cy, double cx, void *M_dev,
                                   void *y_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!cube_dev || !M_dev || !y_dev) return fail(PSH_EINVAL, "darts_rows: NULL pointer");
   if (int rc = check_gram("darts_rows", Nt, Ny, Nx, My, Mx)) return rc;
   const GramArgs a = gram_args(cube_dev, Nt, Ny, Nx, My, Mx, cy, cx);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t total = static_cast<size_t>(a.rows) * (a.ncol + 1);
   hipLaunchKernelGGL(darts_rows, dim3(blocks_for(total)), dim3(kDartsThreads), 0, c.stream, a, static_cast<double2 *>(M_dev),
                      static_cast<double2 *>(y_dev));
@@ -395,7 +383,7 @@ extern "C" int psh_darts_rows_dev(const void *cube_dev, int Nt, int Ny, int Nx, 
 extern "C" int psh_darts_synth_dev(const int *ky_host, const int *kx_host, const void *values_host, int nb, int m, int n, int f32,
                                    void *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!ky_host || !kx_host || !values_host || !out_dev) return fail(PSH_EINVAL, "darts_synth: NULL pointer");
   if (nb < 1 || nb > kDartsMaxBins) return fail(PSH_EUNSUPPORTED, "darts_synth: %d bins (1..%d)", nb, kDartsMaxBins);
   if (m < 1 || n < 1 || m > 65535) return fail(PSH_EINVAL, "darts_synth: shape %d x %d", m, n);
@@ -409,9 +397,6 @@ extern "C" int psh_darts_synth_dev(const int *ky_host, const int *kx_host, const
     bins.v[0][b] = vals[b];
     bins.v[1][b] = vals[nb + b];
   }
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc(static_cast<size_t>(nb) * (n + 2 * static_cast<size_t>(m)) * sizeof(double2))) return rc;
   double2 *ex = blk.as<double2>(), *py = ex + static_cast<size_t>(nb) * n;

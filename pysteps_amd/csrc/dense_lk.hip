@@ -40,16 +40,13 @@ extern "C" int psh_dense_lk_dev(const float *frames_dev, int nframes, int m, int
 extern "C" int psh_dense_lk_uv_dev(const float *frames_dev, int nframes, int m, int n, const psh_lk_params *prm,
                                    float *field_dev, float *field_uv_dev, double *xy_host, double *uv_host, int capacity,
                                    int *count_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (field_uv_dev && !field_dev) return psh::fail(PSH_EINVAL, "dense_lk: the interleaved field without the field itself");
   if (!frames_dev || !prm) return psh::fail(PSH_EINVAL, "dense_lk: NULL pointer");
   if (nframes < 1 || m <= 0 || n <= 0) return psh::fail(PSH_EINVAL, "dense_lk: invalid shape");
   if (!field_dev && !(xy_host && uv_host && count_out))
     return psh::fail(PSH_EINVAL, "dense_lk: neither a dense output nor sparse output buffers given");
   if (prm->max_corners <= 0) return psh::fail(PSH_EINVAL, "dense_lk: max_corners must be positive");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n;
   // PYSTEPS_HIP_TRACE=1: host-side timeline of the call on stderr (where the host waits and works)
   static const bool trace = std::getenv("PYSTEPS_HIP_TRACE") != nullptr;

@@ -257,13 +257,10 @@ extern "C" int psh_detcat_counts_dev(const void *fct_dev, int fct_f64, const voi
                                      size_t npix, const double *thr_fct_host, const double *thr_obs_host, int n_thresholds,
                                      unsigned long long *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!thr_fct_host || !thr_obs_host || !out_dev) return fail(PSH_EINVAL, "detcat: NULL pointer");
   if (int rc = check_fields("detcat", fct_dev, fct_f64, obs_dev, obs_f64, K, npix)) return rc;
   if (n_thresholds < 1 || n_thresholds > 4096) return fail(PSH_EINVAL, "detcat: %d thresholds (1..4096)", n_thresholds);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemsetAsync(out_dev, 0, static_cast<size_t>(K) * n_thresholds * 4 * sizeof(unsigned long long), c.stream));
   return with_real(fct_dev, fct_f64 != 0, [&](auto *fct) {
     return with_real(obs_dev, obs_f64 != 0, [&](auto *obs) {
@@ -276,13 +273,10 @@ extern "C" int psh_detcont_sums_dev(const void *fct_dev, int fct_f64, const void
                                     size_t npix, int conditioning, double thr_fct, double thr_obs,
                                     unsigned long long *counts_dev, double *sums_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!counts_dev || !sums_dev) return fail(PSH_EINVAL, "detcont: NULL pointer");
   if (int rc = check_fields("detcont", fct_dev, fct_f64, obs_dev, obs_f64, K, npix)) return rc;
   if (conditioning < 0 || conditioning > 2) return fail(PSH_EINVAL, "detcont: conditioning %d (0 none, 1 single, 2 double)", conditioning);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc(static_cast<size_t>(K) * det_groups(npix) * sizeof(DetPartial))) return rc;
   DetPartial *part = blk.as<DetPartial>();

@@ -244,15 +244,12 @@ __global__ __launch_bounds__(256) void convert_elements(const Tin *__restrict__ 
 
 extern "C" int psh_db_transform_dev(const float *in_dev, float *out_dev, size_t n, double threshold,
                                     double zerovalue, int inverse) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n == 0) return PSH_OK;
   if (!in_dev || !out_dev) return psh::fail(PSH_EINVAL, "db_transform: NULL pointer");
   if ((reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 3)
     return psh::fail(PSH_EINVAL, "db_transform: buffers must be 4-byte aligned");
   const bool vec = ((reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15) == 0;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const dim3 grid(c.cu_count * 8), block(256);
   // threshold: the number each value is compared with, in the units of the values compared (forward: of R; inverse:
   // linear, of 10^(R/10) - transformation.py:227-228), already rounded the way NumPy would round it
@@ -266,15 +263,12 @@ extern "C" int psh_db_transform_dev(const float *in_dev, float *out_dev, size_t 
 
 extern "C" int psh_field_transform_dev(const void *in_dev, void *out_dev, int f32, size_t n, int op, double p0, double p1,
                                        double threshold, double zerovalue) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n == 0) return PSH_OK;
   if (!in_dev || !out_dev) return psh::fail(PSH_EINVAL, "field_transform: NULL pointer");
   const uintptr_t both = reinterpret_cast<uintptr_t>(in_dev) | reinterpret_cast<uintptr_t>(out_dev);
   if (both & (f32 ? 3 : 7)) return psh::fail(PSH_EINVAL, "field_transform: buffers must be aligned to their element");
   const bool vec = (both & 15) == 0;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const dim3 grid(c.cu_count * 8);
   const psh::TransformArgs a{p0, p1, threshold, zerovalue};
   const int rc = f32 ? psh::launch_transform_op(op, static_cast<const float *>(in_dev), static_cast<float *>(out_dev), n, a, vec, grid, c.stream)
@@ -350,11 +344,8 @@ int field_stats_full_f64(const double *in_dev, size_t n, FieldStats *st) {
 }  // namespace psh
 
 extern "C" int psh_nonfinite_count_f64_dev(const double *in_dev, size_t n, double *count_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if ((!in_dev && n) || !count_out) return psh::fail(PSH_EINVAL, "nonfinite_count: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::FieldStats st;
   if (int rc = psh::field_stats_full_f64(in_dev, n, &st)) return rc;
   *count_out = st.nonfinite;
@@ -363,11 +354,8 @@ extern "C" int psh_nonfinite_count_f64_dev(const double *in_dev, size_t n, doubl
 
 extern "C" int psh_count_above_dev(const float *in_dev, size_t n, double threshold, double *count_out,
                                    double *nanmin_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if ((!in_dev && n) || !count_out) return psh::fail(PSH_EINVAL, "count_above: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::FieldStats st;
   if (int rc = psh::field_stats_full(in_dev, n, &st)) return rc;
   const double lowest = st.nanmin();
@@ -396,12 +384,9 @@ __global__ __launch_bounds__(256) void axpy_f64(double *__restrict__ dst, const 
 }  // namespace psh
 
 extern "C" int psh_axpy_f64_dev(double *dst_dev, const double *src_dev, double alpha, size_t n) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n == 0) return PSH_OK;
   if (!dst_dev || !src_dev) return psh::fail(PSH_EINVAL, "axpy: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n + 255) / 256, static_cast<size_t>(c.cu_count) * 16));
   hipLaunchKernelGGL(psh::axpy_f64, dim3(blocks), dim3(256), 0, c.stream, dst_dev, src_dev, alpha, n);
   PSH_HIP(hipGetLastError());
@@ -409,12 +394,9 @@ extern "C" int psh_axpy_f64_dev(double *dst_dev, const double *src_dev, double a
 }
 
 extern "C" int psh_convert_dev(const void *in_dev, void *out_dev, size_t n, int to_f64) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n == 0) return PSH_OK;
   if (!in_dev || !out_dev) return psh::fail(PSH_EINVAL, "convert: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (to_f64)
     PSH_HIP(psh::launch_convert_f32_f64(static_cast<const float *>(in_dev), static_cast<double *>(out_dev), n, c.stream));
   else
@@ -424,11 +406,8 @@ extern "C" int psh_convert_dev(const void *in_dev, void *out_dev, size_t n, int 
 
 extern "C" int psh_field_stats_dev(const float *in_dev, size_t n, double *min_out, double *max_out,
                                    double *nonfinite_out, double *nanmin_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev && n) return psh::fail(PSH_EINVAL, "field_stats: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::FieldStats st;
   if (int rc = psh::field_stats_full(in_dev, n, &st)) return rc;
   if (min_out) *min_out = st.min_finite;   // +inf if there is no finite value

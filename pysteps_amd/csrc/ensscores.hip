@@ -356,13 +356,10 @@ using psh::fail;
 extern "C" int psh_detcat_pairs_dev(const void *stack_dev, int f64, int K, size_t npix, const double *thr_host, int n_thresholds,
                                     unsigned long long *hits_dev, unsigned long long *events_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!thr_host || !hits_dev || !events_dev) return fail(PSH_EINVAL, "detcat pairs: NULL pointer");
   if (int rc = check_stack("detcat pairs", stack_dev, f64, K, npix)) return rc;
   if (n_thresholds < 1 || n_thresholds > 4096) return fail(PSH_EINVAL, "detcat pairs: %d thresholds (1..4096)", n_thresholds);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc(cat_pairs_partial_bytes(K, npix))) return rc;
   unsigned *part = blk.as<unsigned>();
@@ -377,13 +374,10 @@ extern "C" int psh_detcat_pairs_dev(const void *stack_dev, int f64, int K, size_
 extern "C" int psh_detcont_pairs_dev(const void *stack_dev, int f64, int K, size_t npix, int sum_mask,
                                      unsigned long long *counts_dev, double *sums_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!counts_dev || !sums_dev) return fail(PSH_EINVAL, "detcont pairs: NULL pointer");
   if (int rc = check_stack("detcont pairs", stack_dev, f64, K, npix)) return rc;
   if (sum_mask < 1 || sum_mask >= (1 << kPairSums)) return fail(PSH_EINVAL, "detcont pairs: sum mask %d (1..%d)", sum_mask, (1 << kPairSums) - 1);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int selected = __builtin_popcount(sum_mask);
   psh::Scratch blk;
   if (int rc = blk.alloc(selected == 1   ? cont_pairs_partial_bytes<4, 1>(K, npix)

@@ -188,7 +188,7 @@ extern "C" int psh_ens_products_dev(const void *members_dev, int members_f64, in
                                     int n_thresholds, int prob_ignore_nan, int mean_ignore_nan, int mean_has_thr,
                                     double mean_thr, int accumulate_f64, void *mean_dev, double *probs_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!members_dev) return fail(PSH_EINVAL, "ens_products: NULL member stack");
   if (k < 1 || k > kEnsMaxMembers) return fail(PSH_EINVAL, "ens_products: %d members (1..%d)", k, kEnsMaxMembers);
   if (npix < 1) return fail(PSH_EINVAL, "ens_products: empty planes");
@@ -198,9 +198,6 @@ extern "C" int psh_ens_products_dev(const void *members_dev, int members_f64, in
   if (!probs_dev) n_thresholds = 0;
   if (!mean_dev && n_thresholds == 0) return fail(PSH_EINVAL, "ens_products: no product requested");
   const int mean_mode = !mean_dev ? kMeanNone : (mean_ignore_nan || mean_has_thr) ? kMeanNan : kMeanPlain;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (members_f64)
     return run<double, double>(members_dev, npix, k, thresholds_host, n_thresholds, prob_ignore_nan, mean_mode, mean_has_thr,
                                mean_thr, mean_dev, probs_dev, c.stream);

@@ -706,11 +706,8 @@ using psh::fail;
 
 // numpy.fft.rfft2 of a real (m, n) float64 array -> (m, n/2+1) complex128
 extern "C" int psh_fft_rfft2_dev(const double *in_dev, int m, int n, void *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev || !out_dev) return fail(PSH_EINVAL, "rfft2: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Dft rows, cols;
   if (int rc = psh::check_shape("rfft2", m, n, &rows, &cols)) return rc;
   const int len = 1 << rows.logm;
@@ -755,13 +752,10 @@ bool fft_shape_supported(int m, int n) {
 // numpy.fft.irfft2(X, s=(m, n)) of an (m, n/2+1) complex128 array -> real (m, n) float64; the input is
 // left untouched (the column pass writes into a scratch block)
 extern "C" int psh_fft_irfft2_dev(const void *in_dev, int m, int n, double *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev || !out_dev) return fail(PSH_EINVAL, "irfft2: NULL pointer");
   if (!psh::fft_shape_supported(m, n))
     return fail(PSH_EUNSUPPORTED, "irfft2: (%d,%d) - sides: powers of two up to 8192 or any length up to 4096", m, n);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch scratch;
   if (int rc = scratch.alloc(static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2))) return rc;
   return psh::fft_irfft2_weighted(in_dev, nullptr, m, n, out_dev, scratch.as<void>());
@@ -770,13 +764,10 @@ extern "C" int psh_fft_irfft2_dev(const void *in_dev, int m, int n, double *out_
 // ... and np.min of the result as the order-preserving key psh_steps_mask_dev reads (what psh_field_min_key_dev
 // computes in a sweep of its own): *min_key_dev is set to the identity first, the row pass folds its outputs in
 extern "C" int psh_fft_irfft2_min_dev(const void *in_dev, int m, int n, double *out_dev, unsigned long long *min_key_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev || !out_dev || !min_key_dev) return fail(PSH_EINVAL, "irfft2_min: NULL pointer");
   if (!psh::fft_shape_supported(m, n))
     return fail(PSH_EUNSUPPORTED, "irfft2: (%d,%d) - sides: powers of two up to 8192 or any length up to 4096", m, n);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch scratch;
   if (int rc = scratch.alloc(static_cast<size_t>(m) * (n / 2 + 1) * sizeof(double2))) return rc;
   PSH_HIP(hipMemsetAsync(min_key_dev, 0xff, sizeof(unsigned long long), c.stream));
@@ -785,11 +776,8 @@ extern "C" int psh_fft_irfft2_min_dev(const void *in_dev, int m, int n, double *
 
 // numpy.fft.fft2 / ifft2 of an (m, n) complex128 array (in_dev == out_dev allowed)
 extern "C" int psh_fft_c2c2_dev(const void *in_dev, int m, int n, int inverse, void *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev || !out_dev) return fail(PSH_EINVAL, "fft2: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Dft rows, cols;
   if (int rc = psh::check_shape("fft2", m, n, &rows, &cols)) return rc;
   const int len = 1 << rows.logm;

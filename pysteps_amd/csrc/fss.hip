@@ -280,7 +280,7 @@ extern "C" int psh_fss_sums_dev(const void *fct_dev, int fct_f64, const void *ob
                                 int m, int n, const double *thr_fct_host, const double *thr_obs_host, int n_thresholds,
                                 const double *scales_host, int n_scales, unsigned long long *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!fct_dev || !obs_dev || !thr_fct_host || !thr_obs_host || !scales_host || !out_dev) return fail(PSH_EINVAL, "fss: NULL pointer");
   if (m < 1 || n < 1) return fail(PSH_EINVAL, "fss: invalid shape (%d,%d)", m, n);
   if (m > kFssMaxDim || n > kFssMaxDim) return fail(PSH_EUNSUPPORTED, "fss: shape (%d,%d) (at most %d each way)", m, n, kFssMaxDim);
@@ -298,9 +298,6 @@ extern "C" int psh_fss_sums_dev(const void *fct_dev, int fct_f64, const void *ob
       scales[j] = static_cast<int>(s);
     }
   }
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane_bytes = static_cast<size_t>(m) * (static_cast<size_t>(n) + 1) * sizeof(uint32_t);
   size_t batch = kFssPrefixBytes / plane_bytes;
   batch = batch < 1 ? 1 : (batch > static_cast<size_t>(K) ? K : batch);

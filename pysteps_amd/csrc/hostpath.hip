@@ -105,8 +105,6 @@ struct Ring {
   }
 };
 
-using Lock = std::unique_lock<std::recursive_mutex>;
-
 // host -> device on `stream`; pinned sources go straight, pageable ones through the ring
 int upload(void *dst_dev, const void *src, size_t nbytes, hipStream_t stream, Ring &ring, Lock &lock) {
   if (nbytes == 0) return PSH_OK;
@@ -244,21 +242,22 @@ using psh::fail;
 extern "C" {
 
 int psh_host_alloc(void **host_ptr, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!host_ptr) return fail(PSH_EINVAL, "psh_host_alloc: NULL out pointer");
-  PSH_HIP(hipSetDevice(ctx().device));
   return psh::pinned_alloc(host_ptr, nbytes);
 }
 
 int psh_host_free(void *host_ptr) {
-  if (!ctx().ready) return PSH_OK;  // interpreter shutdown after psh_shutdown: the pool is gone
+  psh::Context &c = ctx();
+  psh::Lock lock(c.mu);
+  if (!c.ready) return PSH_OK;  // interpreter shutdown after psh_shutdown: the pool is gone
   return psh::pinned_free(host_ptr);
 }
 
 int psh_semilag_host(const void *precip, const void *velocity, int m, int n, const double *steps, int T,
                      int n_iter, int interp_order, float outval, const double *disp_prev, double *disp_out,
                      void *out, int flags, int *input_status) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (input_status) *input_status = 0;
   if (int rc = psh::check_semilag(m, n, T, n_iter, interp_order)) return rc;
   if (!velocity || !steps) return fail(PSH_EINVAL, "semilag: NULL velocity/steps");
@@ -266,9 +265,6 @@ int psh_semilag_host(const void *precip, const void *velocity, int m, int n, con
   if (!precip && !disp_out) return fail(PSH_EINVAL, "semilag: precip is NULL but no displacement output was given");
   const bool p64 = (flags & PSH_SL_PRECIP_F64) != 0, v64 = (flags & PSH_SL_VELOCITY_F64) != 0;
   const bool o64 = (flags & PSH_SL_OUT_F64) != 0;
-  psh::Context &c = ctx();
-  psh::Lock lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (!psh::g_down_stream) PSH_HIP(hipStreamCreateWithFlags(&psh::g_down_stream, hipStreamNonBlocking));
   const size_t plane = static_cast<size_t>(m) * n;
   float *d_p = nullptr, *d_v = nullptr, *d_out = nullptr;

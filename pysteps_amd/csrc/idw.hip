@@ -979,13 +979,10 @@ static int idw_check(int L, int k, int m, int n, double dx, double dy, double po
 extern "C" int psh_idw_dev(const float *xy_dev, const float *values_dev, int L, int m, int n,
                            double x0, double dx, double y0, double dy, int k, double power,
                            double dist_offset, double reach_hint, float *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = idw_check(L, k, m, n, dx, dy, power)) return rc;
   if (!xy_dev || !values_dev || !out_dev) return psh::fail(PSH_EINVAL, "idw: NULL pointer");
   if (!(reach_hint > 0.0)) return psh::fail(PSH_EINVAL, "idw: reach_hint must be positive");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::IdwArgs a;
   a.xy = xy_dev;
   a.uv = values_dev;
@@ -1014,7 +1011,7 @@ extern "C" int psh_idw_dev(const float *xy_dev, const float *values_dev, int L, 
 
 // Interpolation onto the unit pixel grid of an (m, n) image with the sample list, its length and
 // the interpolator preamble in device memory (IdwDyn, written by vectors_finish): nothing about
-// the samples is known on the host, the call only queues kernels.  k <= 0: every sample.
+// the samples is known on the host, the call only queues kernels.  k <= 0: every sample.  Lock held by the caller.
 namespace psh {
 int idw_resident(const float *xy_dev, const float *values_dev, int capacity, const IdwDyn *dyn_dev, int m, int n,
                  int k, double power, double dist_offset, float *out_dev, float *out_uv_dev) {
@@ -1023,7 +1020,6 @@ int idw_resident(const float *xy_dev, const float *values_dev, int capacity, con
   if (k > 32) return fail(PSH_EUNSUPPORTED, "idw: k=%d > 32 is not implemented", k);
   if (!(power > 0.0)) return fail(PSH_EINVAL, "idw: power must be positive");
   Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
   IdwArgs a;
   a.xy = xy_dev;
   a.uv = values_dev;
@@ -1053,12 +1049,9 @@ int idw_resident(const float *xy_dev, const float *values_dev, int capacity, con
 extern "C" int psh_idw_host(const double *xy, const double *values, int L, int m, int n, double x0,
                             double dx, double y0, double dy, int k, double power,
                             double dist_offset, double *out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = idw_check(L, k, m, n, dx, dy, power)) return rc;
   if (!xy || !values || !out) return psh::fail(PSH_EINVAL, "idw: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n;
   std::vector<float> h_xy(2 * static_cast<size_t>(L)), h_uv(2 * static_cast<size_t>(L));
   // farthest any sample can be from any grid node: diagonal of the joint bounding box

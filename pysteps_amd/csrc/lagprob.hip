@@ -146,7 +146,7 @@ using psh::fail;
 extern "C" int psh_lagprob_dev(const void *fields_dev, int fields_f64, int T, int m, int n, double threshold,
                                const int *scales_host, const int *span_lo_host, const int *span_hi_host, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (m < 1 || n < 1) return fail(PSH_EINVAL, "lagprob: invalid shape (%d,%d)", m, n);
   if (n > kLagMaxWidth) return fail(PSH_EUNSUPPORTED, "lagprob: width %d (1..%d)", n, kLagMaxWidth);
   if (T < 1 || T > 65536) return fail(PSH_EINVAL, "lagprob: %d planes", T);
@@ -154,9 +154,6 @@ extern "C" int psh_lagprob_dev(const void *fields_dev, int fields_f64, int T, in
   for (int i = 0; i < T; ++i)
     if (scales_host[i] < 1 || scales_host[i] > kLagMaxScale)
       return fail(PSH_EUNSUPPORTED, "lagprob: scale %d (1..%d)", scales_host[i], kLagMaxScale);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc(static_cast<size_t>(m) * (static_cast<size_t>(n) + 1) * sizeof(uint32_t))) return rc;
   uint32_t *prefix = blk.as<uint32_t>();

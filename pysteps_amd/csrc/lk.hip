@@ -2048,10 +2048,7 @@ extern "C" {
 int psh_lk_prepare_dev(const float *frame_dev, int m, int n, int size_opening, int buffer_mask,
                        float *clean_dev, unsigned char *track_u8_dev,
                        unsigned char *feature_u8_dev, float *stats_dev) {
-  PSH_REQUIRE_INIT();
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
+  PSH_ENTER(c);
   if (m <= 0 || n <= 0) return fail(PSH_EINVAL, "lk_prepare: invalid shape (%d,%d)", m, n);
   void *ws = nullptr;
   if (int rc = psh::ensure_lk_ws(psh::lk_prepare_ws_bytes(m, n, false), &ws)) return rc;
@@ -2064,10 +2061,7 @@ int psh_lk_prepare_dev(const float *frame_dev, int m, int n, int size_opening, i
 int psh_lk_prepare_f64_dev(const double *frame_dev, int m, int n, int size_opening, int buffer_mask,
                            float *clean_dev, unsigned char *track_u8_dev,
                            unsigned char *feature_u8_dev, float *stats_dev) {
-  PSH_REQUIRE_INIT();
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
+  PSH_ENTER(c);
   if (m <= 0 || n <= 0) return fail(PSH_EINVAL, "lk_prepare: invalid shape (%d,%d)", m, n);
   psh::Scratch blk;  // [clean64 | partials | dstats]
   if (int rc = blk.alloc(psh::lk_prepare_ws_bytes(m, n, true))) return rc;
@@ -2092,12 +2086,9 @@ static int check_band(const char *who, int m, int n, int e0, int e1, int r0, int
 }
 
 int psh_lk_band_stats_dev(const float *frame_dev, int m, int n, int r0, int r1, float *stats_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frame_dev || !stats_dev) return fail(PSH_EINVAL, "lk_band_stats: NULL pointer");
   if (int rc = check_band("lk_band_stats", m, n, r0, r1, r0, r1)) return rc;
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   void *ws = nullptr;
   if (int rc = psh::ensure_lk_ws(sizeof(float) * 2 * psh::kRedBlocks, &ws)) return rc;
   float *part = static_cast<float *>(ws);
@@ -2111,14 +2102,11 @@ int psh_lk_band_stats_dev(const float *frame_dev, int m, int n, int r0, int r1, 
 
 int psh_lk_band_open_dev(const float *frame_dev, int m, int n, int e0, int e1, int r0, int r1, int size_opening,
                          int buffer_mask, float *clean_dev, float *stats_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frame_dev || !clean_dev || !stats_dev) return fail(PSH_EINVAL, "lk_band_open: NULL pointer");
   if (int rc = check_band("lk_band_open", m, n, e0, e1, r0, r1)) return rc;
   if (size_opening != 0 && size_opening != 3)
     return fail(PSH_EUNSUPPORTED, "lk_prepare: size_opening %d not implemented (0 or 3)", size_opening);
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int ms = e1 - e0;
   const dim3 ogrid = psh::lk_open_grid(ms, n);
   const int nb_open = ogrid.x * ogrid.y;
@@ -2136,12 +2124,9 @@ int psh_lk_band_open_dev(const float *frame_dev, int m, int n, int e0, int e1, i
 
 int psh_lk_band_to_u8_dev(const float *clean_dev, int m, int n, int e0, int e1, int buffer_mask, const float *stats_dev,
                           unsigned char *track_u8_dev, unsigned char *feature_u8_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!clean_dev || !stats_dev || !track_u8_dev) return fail(PSH_EINVAL, "lk_band_to_u8: NULL pointer");
   if (int rc = check_band("lk_band_to_u8", m, n, e0, e1, e0, e1)) return rc;
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t off = static_cast<size_t>(e0) * n, npx = static_cast<size_t>(e1 - e0) * n;
   const int qgrid = static_cast<int>(std::min<size_t>((npx / 4 + 255) / 256 + 1, 4096));
   hipLaunchKernelGGL(psh::lk_to_u8, dim3(qgrid), dim3(256), 0, c.stream, clean_dev + off, e1 - e0, n, buffer_mask,
@@ -2153,14 +2138,11 @@ int psh_lk_band_to_u8_dev(const float *clean_dev, int m, int n, int e0, int e1, 
 
 int psh_lk_band_response_dev(const unsigned char *feature_u8_dev, const float *clean_dev, int m, int n, int e0, int e1,
                              int r0, int r1, int block_size, int buffer_mask, float *stats_dev, float *eig_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!feature_u8_dev || !clean_dev || !stats_dev || !eig_dev) return fail(PSH_EINVAL, "lk_band_response: NULL pointer");
   if (int rc = check_band("lk_band_response", m, n, e0, e1, r0, r1)) return rc;
   if (block_size < 1 || block_size > 2 * psh::kMaxBlockR + 1 || (block_size & 1) == 0)
     return fail(PSH_EUNSUPPORTED, "lk_corners: block_size %d not implemented (odd, <= 7)", block_size);
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int ms = e1 - e0;
   const dim3 rgrid = psh::lk_response_grid(ms, n, block_size);
   const int nb = rgrid.x * rgrid.y;
@@ -2180,13 +2162,10 @@ int psh_lk_band_response_dev(const unsigned char *feature_u8_dev, const float *c
 int psh_lk_band_select_dev(const float *eig_dev, const float *clean_dev, int m, int n, int e0, int e1, int r0, int r1,
                            int buffer_mask, double quality_level, const float *stats_dev,
                            unsigned long long *keys_dev, int cap, int *count_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!eig_dev || !clean_dev || !stats_dev || !keys_dev || !count_dev || cap <= 0)
     return fail(PSH_EINVAL, "lk_band_select: invalid argument");
   if (int rc = check_band("lk_band_select", m, n, e0, e1, r0, r1)) return rc;
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int ms = e1 - e0;
   const size_t off = static_cast<size_t>(e0) * n;
   PSH_HIP(hipMemsetAsync(count_dev, 0, sizeof(int), c.stream));
@@ -2380,8 +2359,6 @@ int lk_corners_resident(const unsigned char *feature_u8_dev, const float *clean_
     return fail(PSH_EUNSUPPORTED, "lk_corners: more than %d corners or 65535 rows / columns are ordered on the host",
                 corner_order_max_corners());
   Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const CornerWs w(m, n, block_size);
   Scratch ws;  // freed stream-ordered: the kernels below are queued in front of any reuse
   if (int rc = ws.alloc(w.bytes)) return rc;
@@ -2412,11 +2389,8 @@ int lk_corners_resident(const unsigned char *feature_u8_dev, const float *clean_
 int psh_lk_corners_launch_dev(const unsigned char *feature_u8_dev, const float *clean_dev,
                               float *stats_dev, int m, int n, int block_size, int buffer_mask,
                               double quality_level, double min_distance, int max_corners) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (int rc = check_corner_args(feature_u8_dev, clean_dev, stats_dev, m, n, block_size, max_corners)) return rc;
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (g_corner_count == kMaxCornerJobs)
     return fail(PSH_EINVAL, "lk_corners: %d corner requests are already in flight", kMaxCornerJobs);
   CornerJob &job = g_corner_jobs[(g_corner_head + g_corner_count) % kMaxCornerJobs];
@@ -2459,11 +2433,8 @@ int psh_lk_corners_launch_dev(const unsigned char *feature_u8_dev, const float *
 }
 
 int psh_lk_corners_finish(float *points_host, int *count_host) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!points_host || !count_host) return fail(PSH_EINVAL, "lk_corners: NULL pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (g_corner_count == 0) return fail(PSH_EINVAL, "lk_corners: no corner request in flight");
   CornerJob &job = g_corner_jobs[g_corner_head];
   g_corner_head = (g_corner_head + 1) % kMaxCornerJobs;
@@ -2569,24 +2540,15 @@ static int lk_pyramids_on(hipStream_t stream, const unsigned char *prev_u8_dev, 
 
 int psh_lk_pyramids_dev(const unsigned char *prev_u8_dev, const unsigned char *next_u8_dev, int m,
                         int n, int win_w, int win_h, int max_level, void **handle_out) {
-  PSH_REQUIRE_INIT();
-  return lk_pyramids_on(ctx().stream, prev_u8_dev, next_u8_dev, m, n, win_w, win_h, max_level, handle_out, nullptr, 0);
+  PSH_ENTER(c);
+  return lk_pyramids_on(c.stream, prev_u8_dev, next_u8_dev, m, n, win_w, win_h, max_level, handle_out, nullptr, 0);
 }
 
 extern "C++" {
 namespace psh {
-// the pyramids of a frame pair on the side stream: they depend on the uint8 renderings only, so
-// they are built while the main stream orders the corner candidates (a single-workgroup kernel)
-int lk_pyramids_beside(const unsigned char *prev_u8_dev, const unsigned char *next_u8_dev, int m, int n, int win_w,
-                       int win_h, int max_level, void **handle_out) {
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  hipStream_t side = nullptr;
-  if (int rc = side_begin(&side)) return rc;
-  return lk_pyramids_on(side, prev_u8_dev, next_u8_dev, m, n, win_w, win_h, max_level, handle_out, nullptr, 0);
-}
-// ... on a side stream the caller has forked already (no new fork: the pyramids then wait for what the side stream
-// waits for, not for whatever the main stream was given in the meantime).  `block` (lk_pyramids_bytes() bytes, from
+// the pyramids of a frame pair on a side stream the caller has forked (they depend on the uint8 renderings only, so
+// they are built while the main stream orders the corner candidates, a single-workgroup kernel): no new fork, the
+// pyramids wait for what the side stream waits for, not for whatever the main stream was given in the meantime.  `block` (lk_pyramids_bytes() bytes, from
 // psh_malloc) has to be taken BEFORE the caller queues anything else on the main stream after the fork: the allocator
 // is ordered on the main stream, a block it hands out later may still be in use by that work, which the side stream
 // does not wait for.  The pyramid set owns the block once the call has succeeded; when it fails - whichever check or
@@ -2595,8 +2557,6 @@ int lk_pyramids_beside(const unsigned char *prev_u8_dev, const unsigned char *ne
 int lk_pyramids_on_side(hipStream_t side, void *block, size_t block_bytes, const unsigned char *prev_u8_dev,
                         const unsigned char *next_u8_dev, int m, int n, int win_w, int win_h, int max_level,
                         void **handle_out) {
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
   Scratch own(block);  // (psh_free of a block of the allocator succeeds and leaves psh_last_error() alone)
   const int rc = lk_pyramids_on(side, prev_u8_dev, next_u8_dev, m, n, win_w, win_h, max_level, handle_out, block, block_bytes);
   if (rc == PSH_OK) (void)own.release();
@@ -2624,7 +2584,7 @@ size_t lk_pyramids_bytes(int m, int n, int win_w, int win_h, int max_level) {
 static int lk_pyramids_on(hipStream_t stream, const unsigned char *prev_u8_dev, const unsigned char *next_u8_dev,
                           int m, int n, int win_w, int win_h, int max_level, void **handle_out, void *block_in,
                           size_t block_in_bytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!handle_out) return fail(PSH_EINVAL, "lk_pyramids: NULL handle pointer");
   *handle_out = nullptr;
   if (m <= 0 || n <= 0) return fail(PSH_EINVAL, "lk_pyramids: invalid shape (%d,%d)", m, n);
@@ -2633,9 +2593,6 @@ static int lk_pyramids_on(hipStream_t stream, const unsigned char *prev_u8_dev, 
     return fail(PSH_EUNSUPPORTED, "lk_track: window (%d,%d) not implemented (3..%d)", win_w, win_h, psh::kMaxWin);
   if (max_level < 0) return fail(PSH_EINVAL, "lk_pyramids: max_level must be >= 0");
   if (max_level >= psh::kMaxLevels) max_level = psh::kMaxLevels - 1;
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   // level geometry (buildOpticalFlowPyramid stops before a level is not larger than the window)
   int rows[psh::kMaxLevels], cols[psh::kMaxLevels], top = 0;
   rows[0] = m;
@@ -2762,7 +2719,7 @@ int psh_lk_pyramids_free(void *handle) {
   if (!handle) return PSH_OK;
   PyramidSet *ps = static_cast<PyramidSet *>(handle);
   int rc = PSH_OK;
-  if (ps->block && ctx().ready) rc = psh_free(ps->block);  // stream-ordered reuse
+  if (ps->block) rc = psh_free(ps->block);  // stream-ordered reuse; PSH_OK after psh_shutdown, which took the block
   delete ps;
   return rc;
 }
@@ -2786,7 +2743,7 @@ int psh_lk_pyramids_shape(void *handle, int level, int *rows, int *cols, int *to
 // was built on, behind the kernels that fill the level, and has arrived when the call returns.
 int psh_lk_pyramids_read(void *handle, int level, int plane, void *host_out, size_t nbytes) {
   if (!handle || !host_out) return fail(PSH_EINVAL, "lk_pyramids_read: NULL pointer");
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   const PyramidSet *ps = static_cast<const PyramidSet *>(handle);
   if (level < 0 || level > ps->pyr.top)
     return fail(PSH_EINVAL, "lk_pyramids_read: level %d outside 0..%d", level, ps->pyr.top);
@@ -2796,9 +2753,6 @@ int psh_lk_pyramids_read(void *handle, int level, int plane, void *host_out, siz
   if (!src) return fail(PSH_EINVAL, "lk_pyramids_read: the set has no gradient image (window of %d columns)", ps->win_w);
   const size_t want = static_cast<size_t>(std::min(L.rows, L.rows_stored)) * L.cols * (plane == 2 ? sizeof(short2) : 1);
   if (nbytes != want) return fail(PSH_EINVAL, "lk_pyramids_read: %zu bytes given, the plane holds %zu", nbytes, want);
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemcpyAsync(host_out, src, want, hipMemcpyDeviceToHost, ps->stream));
   PSH_HIP(hipStreamSynchronize(ps->stream));
   return PSH_OK;
@@ -2839,16 +2793,13 @@ static void launch_lk_track(int npts, const int *npts_dev, hipStream_t stream, c
 int psh_lk_track_pyr_dev(void *handle, const float *points_host, int npts, int max_count,
                          double epsilon, double min_eig_threshold, float *next_points_host,
                          unsigned char *status_host) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!handle) return fail(PSH_EINVAL, "lk_track: NULL pyramid handle");
   if (npts < 0) return fail(PSH_EINVAL, "lk_track: negative point count");
   if (npts == 0) return PSH_OK;
   if (!points_host || !next_points_host || !status_host) return fail(PSH_EINVAL, "lk_track: NULL pointer");
   PyramidSet *ps = static_cast<PyramidSet *>(handle);
   max_count = std::min(std::max(max_count, 0), 100);  // calcOpticalFlowPyrLK clamps the criteria
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t pts_bytes = (static_cast<size_t>(npts) * sizeof(float2) + 255) & ~static_cast<size_t>(255);
   psh::Scratch blk;
   if (int rc = blk.alloc(2 * pts_bytes + static_cast<size_t>(npts))) return rc;
@@ -2897,8 +2848,6 @@ int lk_track_pool(void *pyramid_handle, const float *points_host, const float *p
   PyramidSet *ps = static_cast<PyramidSet *>(pyramid_handle);
   max_count = std::min(std::max(max_count, 0), 100);
   Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t pts_bytes = (static_cast<size_t>(npts) * sizeof(float2) + 255) & ~static_cast<size_t>(255);
   psh::Scratch blk;
   if (int rc = blk.alloc(2 * pts_bytes + static_cast<size_t>(npts))) return rc;

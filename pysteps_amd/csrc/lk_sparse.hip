@@ -1019,15 +1019,12 @@ hipError_t launch_vectors_finish(const double *pool_xy_dev, const double *pool_u
 extern "C" int psh_lk_order_host(const unsigned long long *keys_host, int count, float response_max,
                                  double quality_level, int m, int n, double min_distance, int max_corners,
                                  float *points_host, int *count_host) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!points_host || !count_host || (count > 0 && !keys_host)) return psh::fail(PSH_EINVAL, "lk_order: NULL pointer");
   if (count < 0 || m <= 0 || n <= 0 || max_corners <= 0) return psh::fail(PSH_EINVAL, "lk_order: invalid argument");
   if (!psh::corner_order_supported(m, n, min_distance, max_corners))
     return psh::fail(PSH_EUNSUPPORTED, "lk_order: more than %d corners, 65535 rows / columns or min_distance >= 16383",
                      psh::kMaxCornersDev);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t key_bytes = (static_cast<size_t>(count) * sizeof(unsigned long long) + 255) & ~static_cast<size_t>(255);
   const size_t pts_bytes = static_cast<size_t>(max_corners) * 2 * sizeof(float);
   psh::Scratch blk;
@@ -1064,15 +1061,12 @@ extern "C" int psh_lk_order_host(const unsigned long long *keys_host, int count,
 extern "C" int psh_vectors_finish_host(const double *xy, const double *values, const unsigned char *outlier_flags,
                                        int count, double decl_scale, int m, int n, float *out_xy, float *out_values,
                                        int *out_count, int *out_mode, float *out_const, float *out_reach) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (count < 0 || m <= 0 || n <= 0) return psh::fail(PSH_EINVAL, "vectors_finish: invalid argument");
   if (count > psh::kFinMax) return psh::fail(PSH_EUNSUPPORTED, "vectors_finish: more than %d vectors", psh::kFinMax);
   if (!out_xy || !out_values || !out_count || !out_mode || !out_const || !out_reach ||
       (count > 0 && (!xy || !values || !outlier_flags)))
     return psh::fail(PSH_EINVAL, "vectors_finish: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t cap = static_cast<size_t>(count > 0 ? count : 1);
   const size_t vec = cap * 16, off_uv = vec, off_fl = 2 * vec, off_cnt = (off_fl + cap + 255) & ~static_cast<size_t>(255);
   const size_t off_oxy = off_cnt + 256, off_ouv = off_oxy + cap * 8, off_dyn = off_ouv + cap * 8;

@@ -313,14 +313,11 @@ __global__ __launch_bounds__(64 * kBitsWaves) void mask_from_bits(const unsigned
 extern "C" int psh_dilated_mask_dev(const unsigned char *mask_dev, int m, int n, const unsigned char *kr_host, int kh,
                                     int kw, int r, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!mask_dev || !kr_host || !out_dev) return fail(PSH_EINVAL, "dilated_mask: NULL pointer");
   if (m <= 0 || n <= 0 || kh <= 0 || kw <= 0 || r < 0) return fail(PSH_EINVAL, "dilated_mask: invalid shape");
   if (r > 254) return fail(PSH_EUNSUPPORTED, "dilated_mask: at most 254 rim iterations");
   if (kh > 32767 || kw > 32767) return fail(PSH_EUNSUPPORTED, "dilated_mask: structuring element too large");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   // offsets of the structure's set elements relative to its centre (scipy: size // 2), through the
   // pinned constant slot
   constexpr int kMaxTaps = static_cast<int>(kConstSlotFloats * sizeof(float) / sizeof(short2));
@@ -371,13 +368,10 @@ extern "C" int psh_dilated_mask_dev(const unsigned char *mask_dev, int m, int n,
 extern "C" int psh_steps_incremental_mask_dev(const double *field_dev, int m, int n, double threshold,
                                               const unsigned char *kr_host, int kh, int kw, int r, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || !kr_host || !out_dev) return fail(PSH_EINVAL, "incremental_mask: NULL pointer");
   if (m <= 0 || n <= 0 || kh <= 0 || kw <= 0 || r < 0) return fail(PSH_EINVAL, "incremental_mask: invalid shape");
   if (r > 254) return fail(PSH_EUNSUPPORTED, "incremental_mask: at most 254 rim iterations");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   BitTaps taps;
   int ntaps = 0, reach = 0;
   bool centre = false;

@@ -228,12 +228,9 @@ using psh::fail;
 
 extern "C" int psh_noise_adj_observed_dev(const double *r_dev, size_t plane, double thr1, double thr2,
                                           unsigned char *mask_dev, double *clean_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!r_dev || !mask_dev || !clean_dev) return fail(PSH_EINVAL, "noise_adj_observed: NULL pointer");
   if (plane == 0) return fail(PSH_EINVAL, "noise_adj_observed: empty field");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::observed, dim3(psh::sweep_blocks(plane)), dim3(psh::kThreads), 0, c.stream, r_dev, plane, thr1, thr2,
                      mask_dev, clean_dev);
   PSH_HIP(hipGetLastError());
@@ -241,11 +238,8 @@ extern "C" int psh_noise_adj_observed_dev(const double *r_dev, size_t plane, dou
 }
 
 extern "C" int psh_noise_adj_centre_dev(double *field_dev, size_t n, double mu) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || n == 0) return fail(PSH_EINVAL, "noise_adj_centre: NULL pointer or empty field");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::centre, dim3(psh::sweep_blocks(n)), dim3(psh::kThreads), 0, c.stream, field_dev, n, mu);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
@@ -253,12 +247,9 @@ extern "C" int psh_noise_adj_centre_dev(double *field_dev, size_t n, double mu) 
 
 extern "C" int psh_noise_adj_prepare_dev(double *fields_dev, int nbatch, size_t plane, const unsigned char *mask_dev,
                                          double sigma, double mu, double thr2, double *stats_out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!fields_dev || !mask_dev) return fail(PSH_EINVAL, "noise_adj_prepare: NULL pointer");
   if (nbatch < 1 || nbatch > 65535 || plane == 0) return fail(PSH_EINVAL, "noise_adj_prepare: 1..65535 fields, not empty");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch stats;
   if (int rc = stats.alloc(static_cast<size_t>(nbatch) * sizeof(double2))) return rc;
   // np.std(N) of every realisation: the moments kernels the noise filter standardises with, per plane
@@ -272,11 +263,8 @@ extern "C" int psh_noise_adj_prepare_dev(double *fields_dev, int nbatch, size_t 
 }
 
 extern "C" int psh_mask_count_dev(const unsigned char *mask_dev, size_t plane, unsigned long long *count_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!mask_dev || !count_dev) return fail(PSH_EINVAL, "mask_count: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemsetAsync(count_dev, 0, sizeof(unsigned long long), c.stream));
   if (plane) hipLaunchKernelGGL(psh::mask_count, dim3(std::min(psh::sweep_blocks(plane), 1024u)), dim3(psh::kThreads), 0, c.stream,
                                 mask_dev, plane, count_dev);
@@ -286,13 +274,10 @@ extern "C" int psh_mask_count_dev(const unsigned char *mask_dev, size_t plane, u
 
 extern "C" int psh_masked_moments_dev(const double *planes_dev, int nplanes, size_t plane, const unsigned char *mask_dev,
                                       const unsigned long long *count_dev, int planes_per_block, double *stats_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!planes_dev || !mask_dev || !count_dev || !stats_dev) return fail(PSH_EINVAL, "masked_moments: NULL pointer");
   if (nplanes < 1 || nplanes > 65535 || plane == 0) return fail(PSH_EINVAL, "masked_moments: 1..65535 planes, not empty");
   if (planes_per_block != 1 && planes_per_block != 4) return fail(PSH_EINVAL, "masked_moments: 1 or 4 planes per block");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch partial;
   if (int rc = partial.alloc(static_cast<size_t>(nplanes) * psh::kPartBlocks * sizeof(psh::Part))) return rc;
   psh::Part *part = partial.as<psh::Part>();
@@ -310,13 +295,10 @@ extern "C" int psh_masked_moments_dev(const double *planes_dev, int nplanes, siz
 
 extern "C" int psh_spectrum_level_moments_dev(const void *spec_dev, int nspec, const double *weights_dev, int nlevels, int m,
                                               int n, double *stats_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!spec_dev || !weights_dev || !stats_dev) return fail(PSH_EINVAL, "spectrum_level_moments: NULL pointer");
   if (nlevels < 1 || nlevels > psh::kMaxLevels) return fail(PSH_EUNSUPPORTED, "spectrum_level_moments: 1..%d levels", psh::kMaxLevels);
   if (nspec < 1 || nspec > 65535 || m <= 0 || n <= 1) return fail(PSH_EINVAL, "spectrum_level_moments: invalid shape");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nc = n / 2 + 1;
   const int grid = std::min(m, 1024);  // rows are dealt to the blocks; a function of the shape alone
   psh::Scratch partial;

@@ -380,14 +380,11 @@ bool misaligned(const void *p, bool f32) { return reinterpret_cast<uintptr_t>(p)
 
 extern "C" int psh_nqt_count_le_dev(const void *x_dev, int f32, size_t n, unsigned *count_dev, void *sorted_dev, size_t *n_valid,
                                     double *min_out, double *max_out, float *stage_ms) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!x_dev || !count_dev || !sorted_dev || !n_valid) return fail(PSH_EINVAL, "nqt_count_le: NULL pointer");
   if (n == 0) return fail(PSH_EINVAL, "nqt_count_le: nothing to count");
   if (n > kNqtMaxValues) return fail(PSH_EUNSUPPORTED, "nqt_count_le: more than 2^32 - 1 values");
   if (misaligned(x_dev, f32) || misaligned(sorted_dev, f32)) return fail(PSH_EINVAL, "nqt_count_le: buffers must be aligned to their element");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   if (f32)
     return psh::count_le_impl(static_cast<const float *>(x_dev), n, count_dev, static_cast<float *>(sorted_dev), n_valid, min_out, max_out, stage_ms, c.stream);
   return psh::count_le_impl(static_cast<const double *>(x_dev), n, count_dev, static_cast<double *>(sorted_dev), n_valid, min_out, max_out, stage_ms,
@@ -396,13 +393,10 @@ extern "C" int psh_nqt_count_le_dev(const void *x_dev, int f32, size_t n, unsign
 
 extern "C" int psh_nqt_forward_dev(const void *x_dev, int f32, const unsigned *count_dev, size_t n, size_t n_valid, double a, double zerovalue,
                                    void *out_dev, int out_f32, double *threshold_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!x_dev || !count_dev || !out_dev) return fail(PSH_EINVAL, "nqt_forward: NULL pointer");
   if (n == 0 || n_valid > n || n > kNqtMaxValues) return fail(PSH_EINVAL, "nqt_forward: 1 ... 2^32 - 1 values, n_valid <= n");
   if (misaligned(x_dev, f32) || misaligned(out_dev, out_f32)) return fail(PSH_EINVAL, "nqt_forward: buffers must be aligned to their element");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Smallest sm;
   if (int rc = sm.start(c.stream)) return rc;
   const double den = static_cast<double>(n_valid + 1) - 2.0 * a;  // (n + 1 - 2 * a) of transformation.py:299
@@ -421,12 +415,9 @@ extern "C" int psh_nqt_forward_dev(const void *x_dev, int f32, const unsigned *c
 }
 
 extern "C" int psh_nqt_table_dev(size_t n_valid, double a, double *rqn_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!rqn_dev) return fail(PSH_EINVAL, "nqt_table: NULL pointer");
   if (n_valid == 0 || n_valid > kNqtMaxValues) return fail(PSH_EINVAL, "nqt_table: 1 ... 2^32 - 1 entries");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const double den = static_cast<double>(n_valid + 1) - 2.0 * a;
   hipLaunchKernelGGL(psh::nqt_table, dim3(psh::grid_x(n_valid)), dim3(psh::kThreads), 0, c.stream, n_valid, a, den, rqn_dev);
   PSH_HIP(hipGetLastError());
@@ -435,15 +426,12 @@ extern "C" int psh_nqt_table_dev(size_t n_valid, double a, double *rqn_dev) {
 
 extern "C" int psh_nqt_inverse_dev(const void *x_dev, int f32, size_t n, const double *rqn_dev, const void *sorted_dev, int sorted_f32,
                                    size_t n_table, void *out_dev, int out_f32, double *min_out, double *above_min_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!x_dev || !rqn_dev || !sorted_dev || !out_dev) return fail(PSH_EINVAL, "nqt_inverse: NULL pointer");
   if (n == 0) return fail(PSH_EINVAL, "nqt_inverse: nothing to transform");
   if (n_table < 2) return fail(PSH_EINVAL, "nqt_inverse: the table needs two entries");
   if (misaligned(x_dev, f32) || misaligned(sorted_dev, sorted_f32) || misaligned(out_dev, out_f32) || misaligned(rqn_dev, false))
     return fail(PSH_EINVAL, "nqt_inverse: buffers must be aligned to their element");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Smallest sm;
   if (int rc = sm.start(c.stream)) return rc;
   const dim3 grid(psh::grid_x(n)), block(psh::kThreads);

@@ -916,13 +916,10 @@ static int probmatch_run(const double *initial_dev, const double *target_dev, si
                          int *status_dev, const PmPlan *plan = nullptr, PmPlan *make = nullptr,
                          const PmMask *mask = nullptr) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if ((!make && (!initial_dev || !out_dev)) || (!plan && !target_dev)) return fail(PSH_EINVAL, "probmatch: NULL pointer");
   if (count == 0) return fail(PSH_EINVAL, "probmatch: empty arrays");
   if (count > 0x7fffffffull) return fail(PSH_EUNSUPPORTED, "probmatch: more than 2^31-1 pixels");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
 
   // [header | statistics partials 2 x 2048 | counts 2 x B | starts 2 x B | cursors 2 x B | block sums 2 x 1024 | block offsets 2 x 1024 |
   //  large-bucket lists 2 x cap | scattered target values N | sorted wet target values N |
@@ -1088,34 +1085,29 @@ extern "C" int psh_order_statistic_dev(const double *field_dev, size_t count, si
   if (index >= count) return fail(PSH_EINVAL, "order_statistic: index %zu outside 0..%zu", index, count - 1);
   void *handle = nullptr;
   if (int rc = psh_probmatch_plan_create(field_dev, count, &handle)) return rc;
-  PmPlan *plan = static_cast<PmPlan *>(handle);
-  Context &c = ctx();
-  int rc = PSH_OK;
-  {
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
-    static void *pinned = nullptr;
-    auto run = [&]() -> int {
-      if (int r = persistent_pinned(&pinned, 512)) return r;
-      PmHeader *h = static_cast<PmHeader *>(pinned);
-      PSH_HIP(hipMemcpyAsync(h, plan->blk, sizeof(PmHeader), hipMemcpyDeviceToHost, c.stream));
-      PSH_HIP(hipStreamSynchronize(c.stream));
-      if (h->status != kStOk) return probmatch_status_to_rc(h->status);
-      if (h->n_nan[1] != 0) return fail(PSH_EINVAL, "order_statistic: the field contains NaNs");
-      const size_t zeros = count - h->wet[1];
-      if (index < zeros) {
-        *value_host = h->z[1];
-        return PSH_OK;
-      }
-      double *slot = reinterpret_cast<double *>(static_cast<char *>(pinned) + 256);
-      PSH_HIP(hipMemcpyAsync(slot, plan->tw() + (index - zeros), sizeof(double), hipMemcpyDeviceToHost, c.stream));
-      PSH_HIP(hipStreamSynchronize(c.stream));
-      *value_host = *slot;
-      return PSH_OK;
-    };
-    rc = run();
+  struct PlanOwner {  // destroyed on every return (after the lock below is released; the destroy takes it itself)
+    PmPlan *plan;
+    ~PlanOwner() { (void)psh_probmatch_plan_destroy(plan); }
+  } const owner{static_cast<PmPlan *>(handle)};
+  const PmPlan *plan = owner.plan;
+  PSH_ENTER(c);  // behind the plan's own checks: they answer first, as they always did
+  static void *pinned = nullptr;
+  if (int rc = persistent_pinned(&pinned, 512)) return rc;
+  PmHeader *h = static_cast<PmHeader *>(pinned);
+  PSH_HIP(hipMemcpyAsync(h, plan->blk, sizeof(PmHeader), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  if (h->status != kStOk) return probmatch_status_to_rc(h->status);
+  if (h->n_nan[1] != 0) return fail(PSH_EINVAL, "order_statistic: the field contains NaNs");
+  const size_t zeros = count - h->wet[1];
+  if (index < zeros) {
+    *value_host = h->z[1];
+    return PSH_OK;
   }
-  (void)psh_probmatch_plan_destroy(handle);
-  return rc;
+  double *slot = reinterpret_cast<double *>(static_cast<char *>(pinned) + 256);
+  PSH_HIP(hipMemcpyAsync(slot, plan->tw() + (index - zeros), sizeof(double), hipMemcpyDeviceToHost, c.stream));
+  PSH_HIP(hipStreamSynchronize(c.stream));
+  *value_host = *slot;
+  return PSH_OK;
 }
 
 extern "C" int psh_probmatch_status(int status) {

@@ -349,16 +349,13 @@ extern "C" int psh_crps_sums_dev(const void *fct_dev, int fct_f64, int fct_share
                                  int K, size_t npix, const double *weights_host, unsigned long long *counts_dev,
                                  double *sums_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!fct_dev || !obs_dev || !weights_host || !counts_dev || !sums_dev) return fail(PSH_EINVAL, "crps: NULL pointer");
   if (npix < 1) return fail(PSH_EINVAL, "crps: empty field");
   if (K < 1 || K > kCrpsMaxMembers) return fail(PSH_EINVAL, "crps: %d members (1..%d)", K, kCrpsMaxMembers);
   if (n_planes < 1 || n_planes > 65535) return fail(PSH_EINVAL, "crps: %d observation planes (1..65535)", n_planes);
   if (misaligned(fct_dev, fct_f64) || misaligned(obs_dev, obs_f64))
     return fail(PSH_EINVAL, "crps: a field is not aligned to its element size");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const double *weights = nullptr;
   if (int rc = upload_doubles(static_cast<size_t>(K + 1) * 2, &weights, [&](double *h) {
         for (int i = 0; i < 2 * (K + 1); ++i) h[i] = weights_host[i];
@@ -379,7 +376,7 @@ extern "C" int psh_probbins_dev(const void *prob_dev, int prob_f64, const void *
                                 const double *edges_host, int n_edges, const double *prob_thrs_host, int n_prob_thrs,
                                 unsigned long long *bins_dev, double *sums_dev, unsigned long long *roc_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!prob_dev || !obs_dev) return fail(PSH_EINVAL, "probbins: NULL pointer");
   if (npix < 1) return fail(PSH_EINVAL, "probbins: empty field");
   if (n_edges < 0 || n_edges == 1 || n_edges > kBinsLanes + 1)
@@ -392,9 +389,6 @@ extern "C" int psh_probbins_dev(const void *prob_dev, int prob_f64, const void *
     return fail(PSH_EINVAL, "probbins: NULL pointer");
   if (misaligned(prob_dev, prob_f64) || misaligned(obs_dev, obs_f64))
     return fail(PSH_EINVAL, "probbins: a field is not aligned to its element size");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const double *tables = nullptr;
   if (int rc = upload_doubles(static_cast<size_t>(2) * kBinsLanes + 1, &tables, [&](double *h) {
         for (int e = 0; e <= kBinsLanes; ++e) h[e] = e < n_edges ? edges_host[e] : NAN;

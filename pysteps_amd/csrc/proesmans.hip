@@ -425,12 +425,9 @@ extern "C" int psh_proesmans_sweep_launches(int m, int n) {
 
 extern "C" int psh_proesmans_scale_dev(const void *frames_dev, int f32, size_t count, double *out_dev, double *range_host) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frames_dev || !out_dev || !range_host) return fail(PSH_EINVAL, "proesmans_scale: NULL pointer");
   if (count < 1) return fail(PSH_EINVAL, "proesmans_scale: no values");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   ReduceBlock *rb = nullptr;
   if (int rc = reduce_block(&rb)) return rc;
   const int nb = blocks_1d(count);
@@ -451,12 +448,9 @@ extern "C" int psh_proesmans_scale_dev(const void *frames_dev, int f32, size_t c
 
 extern "C" int psh_proesmans_pyramid_dev(const double *src_dev, int m, int n, double *dst_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!src_dev || !dst_dev) return fail(PSH_EINVAL, "proesmans_pyramid: NULL pointer");
   if (m < 2 || n < 2 || m / 2 > 65535) return fail(PSH_EINVAL, "proesmans_pyramid: shape %d x %d", m, n);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(pyramid_level, grid_2d(m / 2, n / 2), dim3(kThreads), 0, c.stream, src_dev, n, m / 2, n / 2, dst_dev);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
@@ -464,12 +458,9 @@ extern "C" int psh_proesmans_pyramid_dev(const double *src_dev, int m, int n, do
 
 extern "C" int psh_proesmans_gradients_dev(const double *frame_dev, int m, int n, double *grad_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frame_dev || !grad_dev) return fail(PSH_EINVAL, "proesmans_gradients: NULL pointer");
   if (m < 1 || n < 1 || m > 65535) return fail(PSH_EINVAL, "proesmans_gradients: shape %d x %d", m, n);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(gradients, grid_2d(m, n), dim3(kThreads), 0, c.stream, frame_dev, m, n, grad_dev);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
@@ -477,12 +468,9 @@ extern "C" int psh_proesmans_gradients_dev(const double *frame_dev, int m, int n
 
 extern "C" int psh_proesmans_consistency_dev(const double *V_dev, int m, int n, double *gamma_dev, double *raw_dev, double *stats_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!V_dev || !gamma_dev) return fail(PSH_EINVAL, "proesmans_consistency: NULL pointer");
   if (int rc = check_shape("proesmans_consistency", m, n)) return rc;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   ReduceBlock *rb = nullptr;
   if (int rc = reduce_block(&rb)) return rc;
   const size_t plane = static_cast<size_t>(m) * n;
@@ -501,26 +489,20 @@ extern "C" int psh_proesmans_consistency_dev(const double *V_dev, int m, int n, 
 extern "C" int psh_proesmans_sweep_dev(const double *frames_dev, const double *grad_dev, const double *gamma_dev, double *V_dev, int m,
                                        int n, double lam) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frames_dev || !grad_dev || !gamma_dev || !V_dev) return fail(PSH_EINVAL, "proesmans_sweep: NULL pointer");
   if (int rc = check_shape("proesmans_sweep", m, n)) return rc;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   return sweep_on(c.stream, SweepArgs{frames_dev, grad_dev, gamma_dev, V_dev, m, n, lam});
 }
 
 extern "C" int psh_proesmans_next_level_dev(const double *V_prev_dev, int m_prev, int n_prev, double *V_next_dev, int m_next, int n_next) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!V_prev_dev || !V_next_dev) return fail(PSH_EINVAL, "proesmans_next_level: NULL pointer");
   if (m_prev < 1 || n_prev < 1 || m_next < 1 || n_next < 1 || m_next > 65535)
     return fail(PSH_EINVAL, "proesmans_next_level: %d x %d -> %d x %d", m_prev, n_prev, m_next, n_next);
   if (m_next / 2 > m_prev || n_next / 2 > n_prev)
     return fail(PSH_EINVAL, "proesmans_next_level: %d x %d is not the level above %d x %d", m_next, n_next, m_prev, n_prev);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(next_level, grid_2d(m_next, n_next), dim3(kThreads), 0, c.stream, V_prev_dev, m_prev, n_prev, V_next_dev, m_next,
                      n_next);
   PSH_HIP(hipGetLastError());
@@ -530,7 +512,7 @@ extern "C" int psh_proesmans_next_level_dev(const double *V_prev_dev, int m_prev
 extern "C" int psh_proesmans_dev(const double *frames_dev, int m, int n, double lam, int num_iter, int num_levels, int f32,
                                  void *V_dev, void *gamma_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!frames_dev || !V_dev || !gamma_dev) return fail(PSH_EINVAL, "proesmans: NULL pointer");
   if (num_levels < 1 || num_levels > 30 || num_iter < 0) return fail(PSH_EINVAL, "proesmans: num_levels %d, num_iter %d", num_levels, num_iter);
   if (int rc = check_shape("proesmans", m, n)) return rc;
@@ -539,9 +521,6 @@ extern "C" int psh_proesmans_dev(const double *frames_dev, int m, int n, double 
   for (int l = 1; l < num_levels; ++l) lm[l] = lm[l - 1] / 2, ln[l] = ln[l - 1] / 2;
   if (lm[num_levels - 1] < 3 || ln[num_levels - 1] < 3)
     return fail(PSH_EUNSUPPORTED, "proesmans: coarsest level %d x %d (each side at least 3)", lm[num_levels - 1], ln[num_levels - 1]);
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   ReduceBlock *rb = nullptr;
   if (int rc = reduce_block(&rb)) return rc;
   // workspace (doubles): levels 1.. of both frames as (2, m_l, n_l) stacks, G (2, 2, m, n), GAMMA (2, m, n), two V (2, 2, m, n)

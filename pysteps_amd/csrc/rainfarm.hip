@@ -217,12 +217,9 @@ using psh::fail;
 
 extern "C" int psh_rainfarm_spectrum_dev(const double *u_dev, const double *alphas_dev, int K, int M, int N, double vi,
                                          double vj, void *half_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!u_dev || !alphas_dev || !half_dev) return fail(PSH_EINVAL, "rainfarm_spectrum: NULL pointer");
   if (K < 1 || K > 65535 || M < 1 || M > 65535 || N < 1 || N > (1 << 24)) return fail(PSH_EINVAL, "rainfarm_spectrum: invalid shape");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nc = N / 2 + 1;
   hipLaunchKernelGGL(psh::spectrum, dim3((nc + psh::kThreads - 1) / psh::kThreads, M, K), dim3(psh::kThreads), 0, c.stream, u_dev,
                      alphas_dev, M, N, vi, vj, static_cast<double2 *>(half_dev));
@@ -231,12 +228,9 @@ extern "C" int psh_rainfarm_spectrum_dev(const double *u_dev, const double *alph
 }
 
 extern "C" int psh_rainfarm_std_dev(const double *noise_dev, int K, size_t plane, double *stats_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!noise_dev || !stats_dev) return fail(PSH_EINVAL, "rainfarm_std: NULL pointer");
   if (K < 1 || K > 65535 || plane == 0) return fail(PSH_EINVAL, "rainfarm_std: 1..65535 planes, not empty");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch partial;
   if (int rc = partial.alloc(static_cast<size_t>(K) * psh::kPartBlocks * sizeof(psh::dd))) return rc;
   psh::dd *part = partial.as<psh::dd>();
@@ -253,13 +247,10 @@ extern "C" int psh_rainfarm_std_dev(const double *noise_dev, int K, size_t plane
 
 extern "C" int psh_rainfarm_exp_dev(const double *noise_dev, const double *stats_dev, int K, int m, int n, int ds,
                                     double *e_dev, double *agg_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!noise_dev || !stats_dev || !e_dev || !agg_dev) return fail(PSH_EINVAL, "rainfarm_exp: NULL pointer");
   if (!psh::shape_ok(K, m, n, ds) || m > 65535) return fail(PSH_EINVAL, "rainfarm_exp: invalid shape");
   if (ds > 8192) return fail(PSH_EUNSUPPORTED, "rainfarm_exp: ds_factor above 8192");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int cells = std::max(1, psh::kThreads / ds);
   const size_t lds = static_cast<size_t>(cells) * ds * sizeof(double);  // <= 64 KiB
   hipLaunchKernelGGL(psh::exp_aggregate, dim3((n + cells - 1) / cells, m, K), dim3(psh::kThreads), lds, c.stream, noise_dev,
@@ -271,14 +262,11 @@ extern "C" int psh_rainfarm_exp_dev(const double *noise_dev, const double *stats
 extern "C" int psh_rainfarm_finish_dev(const double *e_dev, const double *precip_dev, int precip_planes, const double *agg_dev,
                                        int K, int m, int n, int ds, const double *table_dev, int na, int amin, int has_threshold,
                                        double threshold, int f32, void *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!e_dev || !precip_dev || !agg_dev || !out_dev) return fail(PSH_EINVAL, "rainfarm_finish: NULL pointer");
   if (!psh::shape_ok(K, m, n, ds)) return fail(PSH_EINVAL, "rainfarm_finish: invalid shape");
   if (precip_planes != 1 && precip_planes != K) return fail(PSH_EINVAL, "rainfarm_finish: 1 or K low-resolution planes");
   if (table_dev && (na < 1 || na > 64 || amin > 0 || amin + na - 1 < 0)) return fail(PSH_EINVAL, "rainfarm_finish: invalid table");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int M = m * ds, N = n * ds;
   const size_t stride = precip_planes == 1 ? 0 : static_cast<size_t>(m) * n;
   const dim3 grid((N + psh::kThreads - 1) / psh::kThreads, M, K);

@@ -198,24 +198,18 @@ using psh::fail;
 
 extern "C" int psh_rapsd_counts_dev(int m, int n, int shifted, unsigned long long *counts_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!counts_dev) return fail(PSH_EINVAL, "rapsd_counts: NULL pointer");
   if (int rc = check_shape("rapsd_counts", 1, m, n)) return rc;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   return launch_count(m, n, shifted, counts_dev, c.stream);
 }
 
 extern "C" int psh_rapsd_half_dev(const void *spec_dev, int K, int m, int n, double *out_dev, unsigned long long *counts_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!spec_dev || !out_dev || !counts_dev) return fail(PSH_EINVAL, "rapsd_half: NULL pointer");
   if (int rc = check_shape("rapsd_half", K, m, n)) return rc;
   if (reinterpret_cast<uintptr_t>(spec_dev) % 16) return fail(PSH_EINVAL, "rapsd_half: the spectra are not aligned to 16 bytes");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nb = rapsd_bins(m, n), G = groups_for(m), bx = (nb + kRapsdThreads - 1) / kRapsdThreads;
   psh::Scratch blk;
   if (int rc = blk.alloc(static_cast<size_t>(K) * G * nb * sizeof(dd))) return rc;
@@ -232,13 +226,10 @@ extern "C" int psh_rapsd_half_dev(const void *spec_dev, int K, int m, int n, dou
 extern "C" int psh_rapsd_full_dev(const void *planes_dev, int f64, int K, int m, int n, double *out_dev,
                                   unsigned long long *counts_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!planes_dev || !out_dev || !counts_dev) return fail(PSH_EINVAL, "rapsd_full: NULL pointer");
   if (int rc = check_shape("rapsd_full", K, m, n)) return rc;
   if (reinterpret_cast<uintptr_t>(planes_dev) % (f64 ? 8 : 4)) return fail(PSH_EINVAL, "rapsd_full: the planes are not aligned to their element size");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nb = rapsd_bins(m, n), G = groups_for(m), bx = (nb + kRapsdThreads - 1) / kRapsdThreads;
   psh::Scratch blk;
   if (int rc = blk.alloc(static_cast<size_t>(K) * G * nb * sizeof(dd))) return rc;
@@ -255,11 +246,8 @@ extern "C" int psh_rapsd_full_dev(const void *planes_dev, int f64, int K, int m,
 
 extern "C" int psh_rapsd_nonfinite_dev(const void *in_dev, int f64, size_t count, unsigned long long *counts_host) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev || !counts_host) return fail(PSH_EINVAL, "rapsd_nonfinite: NULL pointer");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch blk;
   if (int rc = blk.alloc(2 * sizeof(unsigned long long))) return rc;
   unsigned long long *acc = blk.as<unsigned long long>();
@@ -279,12 +267,9 @@ extern "C" int psh_rapsd_nonfinite_dev(const void *in_dev, int f64, size_t count
 
 extern "C" int psh_rapsd_fill_nan_dev(const void *in_dev, int f64, size_t count, double fill, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!in_dev || !out_dev) return fail(PSH_EINVAL, "rapsd_fill_nan: NULL pointer");
   if (!count) return PSH_OK;
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t want = (count + kRapsdThreads - 1) / kRapsdThreads;
   const unsigned blocks = static_cast<unsigned>(want < 4096 ? want : 4096);
   with_real(in_dev, f64 != 0, [&](auto *in) {

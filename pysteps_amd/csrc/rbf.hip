@@ -92,14 +92,11 @@ __global__ __launch_bounds__(256) void rbf_eval(const double2 *__restrict__ xy, 
 extern "C" int psh_rbf_eval_dev(const double *xy_dev, const double *weights_dev, int N, int m, int n, double x0, double dx,
                                 double y0, double dy, int function, double epsilon, double *out_dev) {
   using namespace psh;
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!xy_dev || !weights_dev || !out_dev) return fail(PSH_EINVAL, "rbf_eval: NULL pointer");
   if (N <= 0 || m <= 0 || n <= 0) return fail(PSH_EINVAL, "rbf_eval: invalid sizes (N=%d, grid %d x %d)", N, m, n);
   if (function < 0 || function >= kNumRbf) return fail(PSH_EUNSUPPORTED, "rbf_eval: basis function %d not implemented", function);
   if (!(epsilon > 0.0) && function <= kGaussian) return fail(PSH_EINVAL, "rbf_eval: epsilon must be positive");
-  Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const dim3 grid((n + 63) / 64, (m + 4 * kRbfPx - 1) / (4 * kRbfPx)), block(256);
   const double inv_eps2 = function <= kGaussian ? 1.0 / (epsilon * epsilon) : 0.0;
   const double2 *xy = reinterpret_cast<const double2 *>(xy_dev), *w = reinterpret_cast<const double2 *>(weights_dev);

@@ -474,15 +474,12 @@ using psh::fail;
 
 extern "C" int psh_rng_create(int n_streams, const uint32_t *keys_host, const int *pos_host, const int *has_gauss_host,
                               const double *gauss_host, size_t max_draw, int n_draws_hint, void **handle_out) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!handle_out || !keys_host || !pos_host) return fail(PSH_EINVAL, "rng_create: NULL pointer");
   if (n_streams < 1 || n_streams > 4096) return fail(PSH_EINVAL, "rng_create: 1..4096 streams");
   if (max_draw == 0 || max_draw > (size_t(1) << 31)) return fail(PSH_EINVAL, "rng_create: 1..2^31 values per draw");
   for (int b = 0; b < n_streams; ++b)
     if (pos_host[b] < 0 || pos_host[b] > psh::kMtN) return fail(PSH_EINVAL, "rng_create: MT19937 position outside 0..624");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Rng *r = new psh::Rng;
   r->streams = n_streams;
   r->max_draw = max_draw;
@@ -621,14 +618,11 @@ static int rng_prepare(psh::Rng *r, int side, double words_max, hipStream_t *str
 }
 
 extern "C" int psh_rng_randn_dev(void *handle, size_t count, double *out_dev, int side) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   psh::Rng *r = static_cast<psh::Rng *>(handle);
   if (!r || (!out_dev && count)) return fail(PSH_EINVAL, "rng_randn: NULL pointer");
   if (count > r->max_draw) return fail(PSH_EINVAL, "rng_randn: %zu values per stream, the handle was made for %zu", count, r->max_draw);
   if (count == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const unsigned long long pairs_max = (count + 1) / 2;  // no cached value
   const unsigned long long pairs_min = count / 2;        // every stream has one
   const unsigned long long window = psh::window_for(pairs_max);
@@ -665,14 +659,11 @@ extern "C" int psh_rng_randn_dev(void *handle, size_t count, double *out_dev, in
 // random_uniform: low + (high - low) * next_double, two words per value, no rejection: the streams advance by
 // exactly 2 count words; a cached normal value stays cached)
 extern "C" int psh_rng_uniform_dev(void *handle, size_t count, double low, double high, double *out_dev, int side) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   psh::Rng *r = static_cast<psh::Rng *>(handle);
   if (!r || (!out_dev && count)) return fail(PSH_EINVAL, "rng_uniform: NULL pointer");
   if (count > r->max_draw) return fail(PSH_EINVAL, "rng_uniform: %zu values per stream, the handle was made for %zu", count, r->max_draw);
   if (count == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipStream_t s = nullptr;
   const double words = 2.0 * static_cast<double>(count);
   if (int rc = rng_prepare(r, side, words, &s)) return rc;
@@ -694,13 +685,10 @@ extern "C" int psh_rng_uniform_dev(void *handle, size_t count, double low, doubl
 }
 
 extern "C" int psh_rng_wait(void *handle) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   psh::Rng *r = static_cast<psh::Rng *>(handle);
   if (!r) return fail(PSH_EINVAL, "rng_wait: NULL handle");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
   if (r->on_side) {
-    PSH_HIP(hipSetDevice(c.device));
     PSH_HIP(hipStreamWaitEvent(c.stream, r->ready, 0));
     r->on_side = false;
   }
@@ -708,7 +696,7 @@ extern "C" int psh_rng_wait(void *handle) {
 }
 
 extern "C" int psh_rng_check(void *handle) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   psh::Rng *r = static_cast<psh::Rng *>(handle);
   if (!r) return fail(PSH_EINVAL, "rng_check: NULL handle");
   if (*static_cast<volatile int *>(r->err_flag))
@@ -717,12 +705,9 @@ extern "C" int psh_rng_check(void *handle) {
 }
 
 extern "C" int psh_rng_get_state(void *handle, uint32_t *keys_host, int *pos_host, int *has_gauss_host, double *gauss_host) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   psh::Rng *r = static_cast<psh::Rng *>(handle);
   if (!r || !keys_host || !pos_host || !has_gauss_host || !gauss_host) return fail(PSH_EINVAL, "rng_get_state: NULL pointer");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipStreamSynchronize(r->stream));
   PSH_HIP(hipStreamSynchronize(c.stream));
   std::vector<psh::RngDyn> d(r->streams);
@@ -748,10 +733,7 @@ extern "C" int psh_rng_get_state(void *handle, uint32_t *keys_host, int *pos_hos
 }
 
 extern "C" int psh_rng_destroy(void *handle) {
-  PSH_REQUIRE_INIT();
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
+  PSH_ENTER(c);
   psh::rng_free(static_cast<psh::Rng *>(handle));
   return PSH_OK;
 }

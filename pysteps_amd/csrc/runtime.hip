@@ -118,6 +118,11 @@ static int semilag_factor_slot(const float **dev) {
   return PSH_OK;
 }
 
+int bind_device(int device) {  // the device bind of every entry (entry.h)
+  PSH_HIP(hipSetDevice(device));
+  return PSH_OK;
+}
+
 int check_semilag(int m, int n, int T, int n_iter, int order_and_mode) {
   const int order = order_and_mode & 0xff, bmode = (order_and_mode >> 8) & 0xff;
   if (order_and_mode < 0 || (order_and_mode >> 16) != 0 || bmode > PSH_MODE_GRID_WRAP)
@@ -145,7 +150,7 @@ const char *psh_version(void) { return "pysteps_hip 0.1 (gfx950)"; }
 
 int psh_init(int device_id) {
   psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
+  psh::Lock lock(c.mu);
   if (c.ready) {
     if (device_id >= 0 && device_id != c.device)
       return fail(PSH_EINVAL, "already bound to device %d (asked for %d)", c.device, device_id);
@@ -157,7 +162,7 @@ int psh_init(int device_id) {
   if (device_id < 0) device_id = 0;
   if (device_id >= count)
     return fail(PSH_EINVAL, "device %d out of range (%d visible)", device_id, count);
-  PSH_HIP(hipSetDevice(device_id));
+  if (int rc = psh::bind_device(device_id)) return rc;
   hipDeviceProp_t prop;
   PSH_HIP(hipGetDeviceProperties(&prop, device_id));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
@@ -205,9 +210,9 @@ int side_end() {
 
 int psh_shutdown(void) {
   psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
+  psh::Lock lock(c.mu);
   if (!c.ready) return PSH_OK;
-  (void)hipSetDevice(c.device);
+  (void)psh::bind_device(c.device);
   (void)hipStreamSynchronize(c.stream);
   if (c.side) (void)hipStreamSynchronize(c.side);
   psh::registry().release_all();  // every registered block, then every translation unit's hook
@@ -247,10 +252,10 @@ int psh_set_option(const char *key, int value) {
     return PSH_OK;
   }
   if (std::strcmp(key, "trim_cache") == 0) {  // give the cached device blocks back to the driver
-    psh::Context &c = ctx();
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
+    psh::Context &c = ctx();  // not initialised: nothing is cached, and that is no error
+    psh::Lock lock(c.mu);
     if (c.ready) {
-      PSH_HIP(hipSetDevice(c.device));
+      if (int rc = psh::bind_device(c.device)) return rc;
       PSH_HIP(hipStreamSynchronize(c.stream));
       psh::release_cache();
       psh::pinned_release_cache();
@@ -265,10 +270,7 @@ int psh_field_stats_dev(const float *in_dev, size_t n, double *min_out, double *
 
 int psh_device_info(int *device_id, int *cu_count, size_t *hbm_total, size_t *hbm_free,
                     char *name, int name_len) {
-  PSH_REQUIRE_INIT();
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
+  PSH_ENTER(c);
   if (device_id) *device_id = c.device;
   if (cu_count) *cu_count = c.cu_count;
   if (hbm_total || hbm_free) {
@@ -286,11 +288,8 @@ int psh_device_info(int *device_id, int *cu_count, size_t *hbm_total, size_t *hb
 }
 
 int psh_malloc(void **dev_ptr, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!dev_ptr) return fail(PSH_EINVAL, "psh_malloc: NULL out pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   *dev_ptr = nullptr;
   if (nbytes == 0) return PSH_OK;
   nbytes = (nbytes + 255) & ~static_cast<size_t>(255);
@@ -320,10 +319,10 @@ int psh_malloc(void **dev_ptr, size_t nbytes) {
 }
 
 int psh_free(void *dev_ptr) {
-  if (!ctx().ready || !dev_ptr) return PSH_OK;  // after psh_shutdown the block is gone already
   psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
+  psh::Lock lock(c.mu);
+  if (!c.ready || !dev_ptr) return PSH_OK;  // after psh_shutdown the block is gone already
+  if (int rc = psh::bind_device(c.device)) return rc;
   psh::BlockCache &bc = psh::cache();
   auto it = bc.live.find(dev_ptr);
   if (it == bc.live.end()) return fail(PSH_EINVAL, "psh_free: pointer was not allocated by psh_malloc");
@@ -340,74 +339,59 @@ int psh_free(void *dev_ptr) {
 }
 
 int psh_memcpy_h2d(void *dst_dev, const void *src_host, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (nbytes == 0) return PSH_OK;
   if (!dst_dev || !src_host) return fail(PSH_EINVAL, "psh_memcpy_h2d: NULL pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   // pageable source: the runtime stages it, after which the host buffer may be reused
   PSH_HIP(hipMemcpyAsync(dst_dev, src_host, nbytes, hipMemcpyHostToDevice, c.stream));
   return PSH_OK;
 }
 
 int psh_memcpy_d2h(void *dst_host, const void *src_dev, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (nbytes == 0) return PSH_OK;
   if (!dst_host || !src_dev) return fail(PSH_EINVAL, "psh_memcpy_d2h: NULL pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemcpyAsync(dst_host, src_dev, nbytes, hipMemcpyDeviceToHost, c.stream));
   PSH_HIP(hipStreamSynchronize(c.stream));
   return PSH_OK;
 }
 
 int psh_memcpy_d2h_async(void *dst_host, const void *src_dev, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (nbytes == 0) return PSH_OK;
   if (!dst_host || !src_dev) return fail(PSH_EINVAL, "psh_memcpy_d2h_async: NULL pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemcpyAsync(dst_host, src_dev, nbytes, hipMemcpyDeviceToHost, c.stream));
   return PSH_OK;
 }
 
 int psh_memcpy_d2d(void *dst_dev, const void *src_dev, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (nbytes == 0) return PSH_OK;
   if (!dst_dev || !src_dev) return fail(PSH_EINVAL, "psh_memcpy_d2d: NULL pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemcpyAsync(dst_dev, src_dev, nbytes, hipMemcpyDeviceToDevice, c.stream));
   return PSH_OK;
 }
 
 int psh_memset(void *dst_dev, int byte_value, size_t nbytes) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (nbytes == 0) return PSH_OK;
   if (!dst_dev) return fail(PSH_EINVAL, "psh_memset: NULL pointer");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemsetAsync(dst_dev, byte_value, nbytes, c.stream));
   return PSH_OK;
 }
 
 int psh_sync(void) {
-  PSH_REQUIRE_INIT();
-  psh::Context &c = ctx();
-  PSH_HIP(hipSetDevice(c.device));
-  PSH_HIP(hipStreamSynchronize(c.stream));
+  PSH_ENTER(c);
+  const hipStream_t stream = c.stream;
+  lock.unlock();  // a waiting thread does not hold the library (a caller that holds the lock itself, as the registry
+                  // does when it regrows a block, keeps it: the mutex is recursive)
+  PSH_HIP(hipStreamSynchronize(stream));
   return PSH_OK;
 }
 
 int psh_event_create(void **event) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!event) return fail(PSH_EINVAL, "psh_event_create: NULL out pointer");
-  PSH_HIP(hipSetDevice(ctx().device));
   hipEvent_t e;
   PSH_HIP(hipEventCreate(&e));
   *event = e;
@@ -415,25 +399,22 @@ int psh_event_create(void **event) {
 }
 
 int psh_event_destroy(void *event) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (event) PSH_HIP(hipEventDestroy(static_cast<hipEvent_t>(event)));
   return PSH_OK;
 }
 
 int psh_event_record(void *event) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!event) return fail(PSH_EINVAL, "psh_event_record: NULL event");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipEventRecord(static_cast<hipEvent_t>(event), c.stream));
   return PSH_OK;
 }
 
 int psh_event_elapsed_ms(void *start, void *stop, float *ms) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!start || !stop || !ms) return fail(PSH_EINVAL, "psh_event_elapsed_ms: NULL argument");
-  PSH_HIP(hipSetDevice(ctx().device));
+  lock.unlock();  // the wait is for the device, not for the library
   PSH_HIP(hipEventSynchronize(static_cast<hipEvent_t>(stop)));
   PSH_HIP(hipEventElapsedTime(ms, static_cast<hipEvent_t>(start), static_cast<hipEvent_t>(stop)));
   return PSH_OK;
@@ -480,7 +461,7 @@ int psh_semilag_dev(const float *precip_dev, const float *velocity_dev, int m, i
 static int semilag_rows(const float *precip_dev, const float *velocity_dev, const float *velocity_uv_dev, int m, int n,
                         const double *steps_host, int T, int n_iter, int interp_order, float outval, double *disp_dev,
                         int resume, int row_begin, int row_count, float *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (row_begin < 0 || row_count <= 0 || row_begin + row_count > m)
     return fail(PSH_EINVAL, "semilag: row band [%d, %d) outside the %d-row image", row_begin,
                 row_begin + row_count, m);
@@ -492,9 +473,6 @@ static int semilag_rows(const float *precip_dev, const float *velocity_dev, cons
   if (resume < 0 || resume > PSH_SL_RESUME_BASE)
     return fail(PSH_EINVAL, "semilag: resume %d is not 0, 1 or %d (PSH_SL_RESUME_BASE)", resume, PSH_SL_RESUME_BASE);
   if (resume && !disp_dev) return fail(PSH_EINVAL, "semilag: resume without displacement");
-  psh::Context &c = ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   // per-step scale factors through the pinned slot ring (no host synchronisation)
   if (static_cast<size_t>(T) > psh::kConstSlotFloats)
     return fail(PSH_EUNSUPPORTED, "semilag: at most %zu lead steps per call", psh::kConstSlotFloats);

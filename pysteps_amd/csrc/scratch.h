@@ -1,6 +1,6 @@
 // Owner of one psh_malloc block that lives for one call: freed (stream-ordered, as psh_free is) when it goes out of
-// scope, whichever return the function takes.  Declare it AFTER the entry point's lock_guard, so that the free
-// happens with the lock still held.  Host code only; no HIP header needed.
+// scope, whichever return the function takes.  Declare it after the entry point's PSH_ENTER (entry.h), so that the
+// free happens with the lock still held.  Host code only; no HIP header needed.
 #pragma once
 
 #include <cstddef>

@@ -606,13 +606,10 @@ __global__ __launch_bounds__(256) void members_pack(const float *__restrict__ ve
 }  // namespace psh
 
 extern "C" int psh_members_pack_dev(const float *velocity_dev, const float *vhat_dev, int m, int n, float *packed_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (m <= 0 || n <= 0 || !velocity_dev || !packed_dev) return psh::fail(PSH_EINVAL, "members_pack: invalid argument");
   if (static_cast<uint64_t>(m) * n >= (1ull << 28))
     return psh::fail(PSH_EUNSUPPORTED, "members_pack: m*n must be < 2^28 pixels (32-bit byte offsets)");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::members_pack, dim3(4096), dim3(256), 0, c.stream, velocity_dev, vhat_dev,
                      static_cast<size_t>(m) * n, packed_dev);
   PSH_HIP(hipGetLastError());
@@ -620,12 +617,9 @@ extern "C" int psh_members_pack_dev(const float *velocity_dev, const float *vhat
 }
 
 extern "C" int psh_velocity_unit_dev(const float *velocity_dev, int m, int n, float *vhat_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (m <= 0 || n <= 0 || !velocity_dev || !vhat_dev)
     return psh::fail(PSH_EINVAL, "velocity_unit: invalid argument");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n;
   hipLaunchKernelGGL(psh::velocity_unit, dim3(2048), dim3(256), 0, c.stream, velocity_dev, plane, vhat_dev);
   PSH_HIP(hipGetLastError());
@@ -636,7 +630,7 @@ static int members_step(const float *precip_dev, const float *velocity_dev, cons
                         const float *packed_dev, const double *pert_par_host, const double *pert_perp_host, int n_members, int m,
                         int n, const double *steps_host, int T, int n_iter, int interp_order, float outval,
                         void *disp_dev, bool compact, int resume, float *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n_members <= 0 || n_members > 65535)
     return psh::fail(PSH_EINVAL, "semilag_members: member count %d out of range", n_members);
   if (m <= 0 || n <= 0 || static_cast<uint64_t>(m) * n >= (1ull << 29))
@@ -656,9 +650,6 @@ static int members_step(const float *precip_dev, const float *velocity_dev, cons
   const bool pert = vhat_dev != nullptr;
   if (pert && (!pert_par_host || !pert_perp_host))
     return psh::fail(PSH_EINVAL, "semilag_members: unit velocity given without member scalars");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   // per-call constants: T scale factors + 2 scalars per member, through the pinned slot ring
   // (asynchronous: back-to-back member steps queue up without a host round trip)
   const size_t n_const = static_cast<size_t>(T) + 2 * static_cast<size_t>(n_members);
@@ -760,12 +751,9 @@ extern "C" int psh_semilag_members_packed_dev(const float *precip_dev, const flo
 }
 
 static int members_convert(const void *src, void *dst, int n_members, int m, int n, bool to_disp) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!src || !dst || n_members <= 0 || n_members > 65535 || m <= 0 || n <= 0)
     return psh::fail(PSH_EINVAL, "members state conversion: invalid argument");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * n;
   const dim3 grid(static_cast<unsigned>(std::min<size_t>((plane + 255) / 256, 4096)), n_members), block(256);
   if (to_disp) {

@@ -283,7 +283,7 @@ hipError_t launch_outliers_pooled(const double *xy_dev, const double *uv_dev, co
 
 extern "C" int psh_outliers_local_host(const double *xy, const double *values, int n, int k,
                                        double thr, unsigned char *flags) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (n < 0) return psh::fail(PSH_EINVAL, "outliers: negative sample count");
   if (n == 0) return PSH_OK;
   if (!xy || !values || !flags) return psh::fail(PSH_EINVAL, "outliers: NULL pointer");
@@ -295,9 +295,6 @@ extern "C" int psh_outliers_local_host(const double *xy, const double *values, i
     flags[0] = 0;
     return PSH_OK;
   }
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t vec_bytes = static_cast<size_t>(n) * 2 * sizeof(double);
   psh::Scratch blk;
   if (int rc = blk.alloc(2 * vec_bytes + static_cast<size_t>(n))) return rc;

@@ -345,15 +345,12 @@ using psh::fail;
 extern "C" int psh_ssft_war_counts_dev(const double *fields_dev, int nr_fields, int m, int n, const long long *wins_host,
                                        int nwin, const double *tiles_dev, size_t tiles_count,
                                        unsigned long long *counts_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!fields_dev || !wins_host || !counts_dev) return fail(PSH_EINVAL, "ssft_war_counts: NULL pointer");
   if (nr_fields < 1 || m < 1 || n < 1 || m > 65535 || n > 65535) return fail(PSH_EINVAL, "ssft_war_counts: invalid shape");
   if (nwin < 1 || nwin > 65535) return fail(PSH_EINVAL, "ssft_war_counts: 1..65535 windows");
   std::vector<psh::Win> wins;
   if (int rc = psh::read_windows("ssft_war_counts", wins_host, nwin, m, n, tiles_count, tiles_dev != nullptr, 1 << 30, &wins)) return rc;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::Scratch table;
   const size_t bytes = static_cast<size_t>(nwin) * psh::kWinFields * sizeof(long long);
   if (int rc = table.alloc(bytes)) return rc;
@@ -371,7 +368,7 @@ extern "C" int psh_ssft_war_counts_dev(const double *fields_dev, int nr_fields, 
 extern "C" int psh_ssft_local_filters_dev(const double *fields_dev, int nr_fields, int m, int n, const long long *wins_host,
                                           int nwin, const double *tiles_dev, size_t tiles_count, int taper_after, int nplanes,
                                           double *planes_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!fields_dev || !wins_host || !planes_dev) return fail(PSH_EINVAL, "ssft_local_filters: NULL pointer");
   if (nr_fields < 1 || nr_fields > 65535 || nwin < 1 || nplanes < 1)
     return fail(PSH_EINVAL, "ssft_local_filters: 1..65535 fields, at least one window and plane");
@@ -379,9 +376,6 @@ extern "C" int psh_ssft_local_filters_dev(const double *fields_dev, int nr_field
     return fail(PSH_EUNSUPPORTED, "ssft_local_filters: (%d,%d) - sides: powers of two up to 8192 or any length up to 4096", m, n);
   std::vector<psh::Win> wins;
   if (int rc = psh::read_windows("ssft_local_filters", wins_host, nwin, m, n, tiles_count, tiles_dev != nullptr, nplanes, &wins)) return rc;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nc = n / 2 + 1;
   const size_t plane = static_cast<size_t>(m) * n, half = static_cast<size_t>(m) * nc;
   const size_t spec_bytes = half * sizeof(double2), part_bytes = 2 * psh::kRowBlocks * sizeof(psh::dd);
@@ -440,12 +434,9 @@ extern "C" int psh_ssft_local_filters_dev(const double *fields_dev, int nr_field
 }
 
 extern "C" int psh_ssft_merge_dev(double *plane_dev, const double *weights_dev, const double *newfilter_dev, size_t count) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!plane_dev || !weights_dev || !newfilter_dev) return fail(PSH_EINVAL, "ssft_merge: NULL pointer");
   if (count == 0) return fail(PSH_EINVAL, "ssft_merge: empty plane");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::merge, dim3(psh::sweep_blocks(count)), dim3(psh::kThreads), 0, c.stream, plane_dev, weights_dev,
                      newfilter_dev, count);
   PSH_HIP(hipGetLastError());
@@ -455,16 +446,13 @@ extern "C" int psh_ssft_merge_dev(double *plane_dev, const double *weights_dev, 
 extern "C" int psh_ssft_generate_dev(const double *white_dev, int K, int m, int n, const double *planes_dev, int nplanes,
                                      const long long *wins_host, int nwin, const double *tiles_dev, size_t tiles_count,
                                      const double *sM_dev, double *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!white_dev || !planes_dev || !wins_host || !sM_dev || !out_dev) return fail(PSH_EINVAL, "ssft_generate: NULL pointer");
   if (K < 1 || K > 65535 || nplanes < 1 || nwin < 1) return fail(PSH_EINVAL, "ssft_generate: 1..65535 fields, at least one plane and window");
   if (!psh::shape_ok(m, n))
     return fail(PSH_EUNSUPPORTED, "ssft_generate: (%d,%d) - sides: powers of two up to 8192 or any length up to 4096", m, n);
   std::vector<psh::Win> wins;
   if (int rc = psh::read_windows("ssft_generate", wins_host, nwin, m, n, tiles_count, tiles_dev != nullptr, nplanes, &wins)) return rc;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nc = n / 2 + 1;
   const size_t plane = static_cast<size_t>(m) * n, half = static_cast<size_t>(m) * nc;
   const size_t spec_bytes = half * sizeof(double2), field_bytes = plane * sizeof(double);

@@ -520,16 +520,13 @@ static int ar_recompose_run(double *cascades_dev, int nlevels, int p, size_t pla
                             const double *eps_dev, const double *eps_stats_dev, const double *eps_scale_host,
                             const double *mu_host, const double *sigma_host, double *field_dev,
                             unsigned long long *min_key_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!cascades_dev || !phi_host || !mu_host || !sigma_host || !field_dev)
     return fail(PSH_EINVAL, "steps_ar_recompose: NULL pointer");
   if (nlevels < 1 || nlevels > psh::kMaxLevels || p < 1 || p > psh::kMaxOrder)
     return fail(PSH_EUNSUPPORTED, "steps_ar_recompose: 1..%d cascade levels, AR order 1..%d", psh::kMaxLevels, psh::kMaxOrder);
   if (plane == 0 || head < 0 || head >= p) return fail(PSH_EINVAL, "steps_ar_recompose: empty plane or ring head outside 0..p-1");
   if (eps_dev && !eps_scale_host) return fail(PSH_EINVAL, "steps_ar_recompose: eps without its scale factors");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::ArRecompose a;
   for (int k = 0; k < nlevels; ++k) {
     for (int j = 0; j <= p; ++j) a.phi[k][j] = phi_host[static_cast<size_t>(k) * (p + 1) + j];
@@ -567,13 +564,10 @@ extern "C" int psh_steps_ar_recompose_raw_dev(double *cascades_dev, int nlevels,
 
 extern "C" int psh_steps_mask_dev(double *field_dev, size_t n, const double *grey_mask_dev, const unsigned char *keep_mask_dev,
                                   const unsigned long long *min_key_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || !min_key_dev || (!grey_mask_dev == !keep_mask_dev))
     return fail(PSH_EINVAL, "steps_mask: field, minimum and exactly one of the two masks are required");
   if (n == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::apply_mask, dim3(psh::grid_for(n)), dim3(psh::kThreads), 0, c.stream, field_dev, n, grey_mask_dev,
                      keep_mask_dev, min_key_dev);
   PSH_HIP(hipGetLastError());
@@ -581,12 +575,9 @@ extern "C" int psh_steps_mask_dev(double *field_dev, size_t n, const double *gre
 }
 
 extern "C" int psh_steps_mean_shift_dev(double *field_dev, size_t n, double threshold, double mu_0) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev) return fail(PSH_EINVAL, "steps_mean_shift: NULL pointer");
   if (n == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nparts = 1024;
   psh::Scratch partial;
   if (int rc = partial.alloc(nparts * sizeof(double2))) return rc;
@@ -599,36 +590,27 @@ extern "C" int psh_steps_mean_shift_dev(double *field_dev, size_t n, double thre
 }
 
 extern "C" int psh_ge_mask_dev(const double *field_dev, size_t n, double threshold, unsigned char *out_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || !out_dev) return fail(PSH_EINVAL, "ge_mask: NULL pointer");
   if (n == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::ge_mask, dim3(psh::grid_for(n)), dim3(psh::kThreads), 0, c.stream, field_dev, n, threshold, out_dev);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
 extern "C" int psh_nan_where_dev(double *field_dev, const unsigned char *mask_dev, size_t n) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || !mask_dev) return fail(PSH_EINVAL, "nan_where: NULL pointer");
   if (n == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::nan_where, dim3(psh::grid_for(n)), dim3(psh::kThreads), 0, c.stream, field_dev, mask_dev, n);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }
 
 extern "C" int psh_lerp_dev(const double *a_dev, const double *b_dev, double w, double *out_dev, size_t n) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!a_dev || !b_dev || !out_dev) return fail(PSH_EINVAL, "lerp: NULL pointer");
   if (n == 0) return PSH_OK;
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::lerp, dim3(psh::grid_for(n)), dim3(psh::kThreads), 0, c.stream, a_dev, b_dev, w, out_dev, n);
   PSH_HIP(hipGetLastError());
   return PSH_OK;
@@ -637,12 +619,9 @@ extern "C" int psh_lerp_dev(const double *a_dev, const double *b_dev, double w, 
 // ---- spectral member update (see the kernels above) -------------------------------------------------
 extern "C" int psh_steps_spectral_sums_dev(const void *noise_spec_dev, const double *filter_dev, const double *weights_dev,
                                            int nlevels, int m, int n, double *sums_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!noise_spec_dev || !filter_dev || !weights_dev || !sums_dev) return fail(PSH_EINVAL, "steps_spectral_sums: NULL pointer");
   if (nlevels < 1 || nlevels > psh::kMaxLevels || m <= 0 || n <= 1) return fail(PSH_EUNSUPPORTED, "steps_spectral_sums: 1..%d levels", psh::kMaxLevels);
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const int nc = n / 2 + 1;
   const int grid = std::min(m, 1024);  // rows are dealt to the workgroups
   psh::Scratch partial;
@@ -659,16 +638,13 @@ extern "C" int psh_steps_spectral_ar_dev(void *cascades_dev, int nlevels, int p,
                                          const void *noise_spec_dev, const double *filter_dev, const double *weights_dev,
                                          const double *sums_dev, const double *noise_std_host, const double *mu_host,
                                          const double *sigma_host, void *field_spec_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!cascades_dev || !phi_host || !noise_spec_dev || !filter_dev || !weights_dev || !sums_dev || !noise_std_host || !mu_host ||
       !sigma_host || !field_spec_dev)
     return fail(PSH_EINVAL, "steps_spectral_ar: NULL pointer");
   if (nlevels < 1 || nlevels > psh::kMaxLevels || p < 1 || p > psh::kMaxOrder)
     return fail(PSH_EUNSUPPORTED, "steps_spectral_ar: 1..%d cascade levels, AR order 1..%d", psh::kMaxLevels, psh::kMaxOrder);
   if (m <= 0 || n <= 1 || head < 0 || head >= p) return fail(PSH_EINVAL, "steps_spectral_ar: invalid shape or ring head");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   const size_t plane = static_cast<size_t>(m) * (n / 2 + 1);
   const double mn = static_cast<double>(m) * static_cast<double>(n);
   psh::SpectralAr a;
@@ -691,11 +667,8 @@ extern "C" int psh_steps_spectral_ar_dev(void *cascades_dev, int nlevels, int p,
 }
 
 extern "C" int psh_field_min_key_dev(const double *field_dev, size_t n, unsigned long long *min_key_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!field_dev || !min_key_dev || n == 0) return fail(PSH_EINVAL, "field_min_key: NULL pointer or empty field");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   PSH_HIP(hipMemsetAsync(min_key_dev, 0xff, sizeof(unsigned long long), c.stream));
   // (few workgroups: every wave ends with an atomic on one address)
   hipLaunchKernelGGL(psh::field_min_key, dim3(std::min<unsigned>(psh::grid_for(n), 1024u)), dim3(psh::kThreads), 0, c.stream, field_dev, n,
@@ -708,7 +681,7 @@ extern "C" int psh_steps_phase_ar_dev(void *cascades_dev, int nlevels, int p, in
                                       const double *theta_dev, const double *filter_dev, const double *weights_dev,
                                       double inv_std_noise, const double *inv_std_levels_host, const double *noise_std_host,
                                       const double *mu_host, const double *sigma_host, void *field_spec_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!cascades_dev || !phi_host || !weights_dev || !mu_host || !sigma_host || !field_spec_dev)
     return fail(PSH_EINVAL, "steps_phase_ar: NULL pointer");
   if (theta_dev && (!filter_dev || !inv_std_levels_host || !noise_std_host))
@@ -716,9 +689,6 @@ extern "C" int psh_steps_phase_ar_dev(void *cascades_dev, int nlevels, int p, in
   if (nlevels < 1 || nlevels > psh::kMaxLevels || p < 1 || p > psh::kMaxOrder)
     return fail(PSH_EUNSUPPORTED, "steps_phase_ar: 1..%d cascade levels, AR order 1..%d", psh::kMaxLevels, psh::kMaxOrder);
   if (m <= 0 || n <= 1 || head < 0 || head >= p) return fail(PSH_EINVAL, "steps_phase_ar: invalid shape or ring head");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   psh::PhaseAr a;
   for (int k = 0; k < psh::kMaxLevels; ++k) {
     for (int j = 0; j <= psh::kMaxOrder; ++j) a.phi[k][j] = (k < nlevels && j <= p) ? phi_host[static_cast<size_t>(k) * (p + 1) + j] : 0.0;
@@ -744,12 +714,9 @@ extern "C" int psh_steps_phase_ar_dev(void *cascades_dev, int nlevels, int p, in
 //                                array of this level, the number of kept coefficients behind them
 //   psh_expand_compact_c128_dev  dst (m, nc) complex128 = src scattered to the kept coefficients, zero elsewhere
 extern "C" int psh_mask_row_offsets_dev(const double *weights_dev, int m, int nc, int *offsets_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!weights_dev || !offsets_dev) return fail(PSH_EINVAL, "mask_row_offsets: NULL pointer");
   if (m <= 0 || m > 8192 || nc <= 0) return fail(PSH_EUNSUPPORTED, "mask_row_offsets: 1..8192 rows");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::mask_row_counts, dim3(m), dim3(psh::kThreads), 0, c.stream, weights_dev, nc, offsets_dev);
   hipLaunchKernelGGL(psh::scan_rows, dim3(1), dim3(psh::kThreads), 0, c.stream, offsets_dev, m);
   PSH_HIP(hipGetLastError());
@@ -758,12 +725,9 @@ extern "C" int psh_mask_row_offsets_dev(const double *weights_dev, int m, int nc
 
 extern "C" int psh_expand_compact_c128_dev(const double *weights_dev, int m, int nc, const int *offsets_dev, const void *src_dev,
                                            void *dst_dev) {
-  PSH_REQUIRE_INIT();
+  PSH_ENTER(c);
   if (!weights_dev || !offsets_dev || !src_dev || !dst_dev) return fail(PSH_EINVAL, "expand_compact: NULL pointer");
   if (m <= 0 || nc <= 0) return fail(PSH_EINVAL, "expand_compact: invalid shape");
-  psh::Context &c = psh::ctx();
-  std::lock_guard<std::recursive_mutex> lock(c.mu);
-  PSH_HIP(hipSetDevice(c.device));
   hipLaunchKernelGGL(psh::expand_compact, dim3(m), dim3(psh::kThreads), 0, c.stream, weights_dev, nc, offsets_dev,
                      static_cast<const double2 *>(src_dev), static_cast<double2 *>(dst_dev));
   PSH_HIP(hipGetLastError());

@@ -209,6 +209,15 @@ def main():
         rc = lib.psh_shutdown()
         assert rc == 0, ("psh_shutdown", number, rc, _lib.last_error())
         assert lib.psh_free(None) == 0 and lib.psh_sync() == _lib.PSH_ENOTINIT
+    # after the last shutdown every entry point answers what it answers before the first psh_init (in-process: none of
+    # these calls gets as far as the device, and a process that has opened the GPU does not fork)
+    from helpers import entry_points
+    from test_entry_points_cpu import EXPECTED
+
+    got = {name: entry_points.call(lib, name) for name in entry_points.names()}
+    wrong = {name: (got[name], EXPECTED[name]) for name in EXPECTED if got.get(name) != EXPECTED[name]}
+    assert sorted(got) == sorted(EXPECTED) and not wrong, wrong
+    print("after the last shutdown: %d entry points answer as before psh_init" % len(got))
     print("hbm_free after each psh_init: %s" % free)
     print("shutdown cycles: ok")
     return 0
