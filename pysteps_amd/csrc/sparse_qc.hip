@@ -5,14 +5,25 @@
 // (N,2), k nearest neighbours): for every vector the k nearest OTHER vectors
 // (cKDTree k+1 query minus the first hit, :221-224), z = uv - mean(neighbours),
 // C = cov(neighbours, ddof=1), outlier iff sqrt(z^T C^-1 z) > thr; singular C ->
-// not an outlier (:239-243).
+// not an outlier (:239-243), which includes fewer than three neighbours (rank < 2).
 //
 // N is a few thousand at most.  One WAVE owns one vector: the 64 lanes compute the
-// N squared distances into an LDS key array (distance bits << 32 | index, so that a
-// single 64-bit minimum also breaks ties by the lower index - cKDTree's own tie
-// order is unspecified), then the k+1 nearest are extracted one by one with a wave
-// minimum; the owner lane retires the key and rescans its N/64 entries.  Sums for
-// mean / covariance are accumulated in float64 relative to the vector itself.
+// N keys (distance bits << 32 | index), then the kk = min(N, k + 1) smallest are
+// extracted one by one with a wave minimum, 64 to a chunk.  Up to 2048 vectors every
+// lane sorts its keys once in registers and pops the next one; above, the keys sit in
+// LDS and the owner lane retires the key and rescans its N/64 entries.
+//
+// What is computed in which precision (pinned by tests/test_outliers_gpu.py):
+//  * position differences dx, dy and dx*dx + dy*dy are float64;
+//  * the ORDERING KEY is that sum rounded to float32, then the index: two neighbours
+//    whose float64 squared distances round to one float32 are taken in index order,
+//    not in distance order, and exact ties go to the lower index (cKDTree's own tie
+//    order is unspecified);
+//  * the first extracted key is dropped: the vector itself, or - at a duplicate
+//    position - the vector with the lowest index there (then the tested vector stays
+//    among its own neighbours);
+//  * sums for mean / covariance (float64, relative to the vector itself, in extraction
+//    order) and the Mahalanobis test are float64.
 // Runtime ~ 10 us; it exists to keep the 2-4 ms host k-d tree query off the critical
 // path of a nowcast step.
 #include <vector>
@@ -52,6 +63,29 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   const unsigned m_hi = wave_min_u32(hi);
   const unsigned m_lo = wave_min_u32(hi == m_hi ? lo : 0xffffffffu);
   return (static_cast<unsigned long long>(m_hi) << 32) | m_lo;
+}
+
+// Lane 0's finish, shared by the three kernels: the Mahalanobis test from the one-pass sums of the cnt neighbour
+// vectors (taken relative to the tested vector, so that vector sits at the origin).
+//  * Fewer than three neighbours: not an outlier.  The covariance of cnt points has rank <= cnt - 1, so two of them
+//    never give an invertible 2 x 2 matrix; det would be the rounding residue of a product that is 0 in exact
+//    arithmetic, of either sign.
+//  * No contraction in here.  For collinear neighbour vectors (v = u, v = 2u, v = -u) caa, cab and cbb agree up to
+//    exact powers of two and det = caa*cbb - cab*cab is exactly 0 with ROUNDED products, as on the host; fused into
+//    fma(caa, cbb, -(cab*cab)) it is the rounding error of cab*cab instead, "det != 0" passes and md2 becomes the
+//    ratio of two residues (dozens of vectors of a collinear field were flagged that way).
+__device__ __forceinline__ bool mahalanobis_outlier(int cnt, double sa, double sb, double saa, double sab, double sbb,
+                                                    double thr) {
+#pragma clang fp contract(off)
+  if (cnt < 3) return false;
+  const double ma = sa / cnt, mb = sb / cnt;  // neighbour mean relative to this vector
+  const double dof = cnt - 1;
+  const double caa = (saa - sa * ma) / dof, cab = (sab - sa * mb) / dof, cbb = (sbb - sb * mb) / dof;
+  const double det = caa * cbb - cab * cab;
+  if (det == 0.0 || !isfinite(det)) return false;  // singular covariance: not an outlier
+  const double zu = -ma, zv = -mb;  // this vector minus the neighbour mean
+  const double md2 = (zu * zu * cbb - 2.0 * zu * zv * cab + zv * zv * caa) / det;
+  return sqrt(md2) > thr;
 }
 
 __global__ __launch_bounds__(64) void outliers_local(const double2 *__restrict__ xy,
@@ -128,20 +162,7 @@ __global__ __launch_bounds__(64) void outliers_local(const double2 *__restrict__
     __syncthreads();
   }
   if (lane != 0) return;
-  bool out = false;
-  if (cnt >= 2) {
-    const double ma = sa / cnt, mb = sb / cnt;  // neighbour mean relative to this vector
-    const double dof = cnt - 1;
-    const double caa = (saa - sa * ma) / dof, cab = (sab - sa * mb) / dof,
-                 cbb = (sbb - sb * mb) / dof;
-    const double det = caa * cbb - cab * cab;
-    if (det != 0.0 && isfinite(det)) {
-      const double zu = -ma, zv = -mb;  // this vector minus the neighbour mean
-      const double md2 = (zu * zu * cbb - 2.0 * zu * zv * cab + zv * zv * caa) / det;
-      out = sqrt(md2) > thr;
-    }
-  }
-  flags[i] = out ? 1 : 0;
+  flags[i] = mahalanobis_outlier(cnt, sa, sb, saa, sab, sbb, thr) ? 1 : 0;
 }
 
 // The same test with every lane's keys SORTED once (register sorting network), for up to 64 x KPER
@@ -238,20 +259,7 @@ __global__ __launch_bounds__(64) void outliers_local_sorted(const double2 *__res
     __syncthreads();
   }
   if (lane != 0) return;
-  bool out = false;
-  if (cnt >= 2) {
-    const double ma = sa / cnt, mb = sb / cnt;  // neighbour mean relative to this vector
-    const double dof = cnt - 1;
-    const double caa = (saa - sa * ma) / dof, cab = (sab - sa * mb) / dof,
-                 cbb = (sbb - sb * mb) / dof;
-    const double det = caa * cbb - cab * cab;
-    if (det != 0.0 && isfinite(det)) {
-      const double zu = -ma, zv = -mb;  // this vector minus the neighbour mean
-      const double md2 = (zu * zu * cbb - 2.0 * zu * zv * cab + zv * zv * caa) / det;
-      out = sqrt(md2) > thr;
-    }
-  }
-  flags[i] = out ? 1 : 0;
+  flags[i] = mahalanobis_outlier(cnt, sa, sb, saa, sab, sbb, thr) ? 1 : 0;
 }
 
 // picks the kernel by the number of vectors the launch may see

@@ -218,6 +218,9 @@ def detect_outliers(input_array, thr, coord=None, k=None, verbose=False):
                 )
                 md = np.zeros(nsamples)
                 ok = np.isfinite(cov).all(axis=(1, 2))
+                # the covariance of c points has rank <= c - 1: with no more neighbours than variables it is
+                # singular in exact arithmetic, and a determinant test would only see the rounding residue
+                ok &= neigh.shape[1] > nvar
                 if nvar == 2:
                     ok &= (cov[:, 0, 0] * cov[:, 1, 1] - cov[:, 0, 1] * cov[:, 1, 0]) != 0.0
                 else:
@@ -236,10 +239,16 @@ def detect_outliers(input_array, thr, coord=None, k=None, verbose=False):
 
 def detect_outliers_device(input_array, thr, coord, k, verbose=False):
     """Local multivariate test of :func:`detect_outliers` for 2-vectors with 2-d
-    coordinates, evaluated by the HIP kernel ``csrc/sparse_qc.hip`` (float64, brute
-    force k-NN, ties -> lower index).  Same result as the host version except where
-    the k-th and (k+1)-th neighbours are exactly equidistant (cKDTree's tie order is
-    unspecified).  Other input shapes are routed to the host implementation."""
+    coordinates, evaluated by the HIP kernels of ``csrc/sparse_qc.hip`` (brute force
+    k-NN).  Position differences, the neighbour sums and the Mahalanobis test are
+    float64.  The neighbours are ordered by the squared distance ROUNDED TO FLOAT32,
+    then by the lower index: two neighbours whose float64 squared distances round to
+    the same float32 are taken in index order, and exact ties go to the lower index.
+    The first hit is dropped even when it is not the vector itself but a vector with
+    a lower index at the same position.  Same result as the host version except at
+    such ties and near-ties of the k-th and (k+1)-th neighbours (cKDTree's tie order
+    is unspecified).  Other input shapes, and more than 8192 vectors, are routed to
+    the host implementation."""
     from .. import _lib  # noqa: PLC0415
 
     values = np.ascontiguousarray(input_array, dtype=np.float64)
