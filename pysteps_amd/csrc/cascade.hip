@@ -13,8 +13,10 @@
 //    reference's random stream is part of its result).
 //  * psh_ar_iterate_dev        - pysteps/timeseries/autoregression.py:1020-1070 (iterate_ar_model): one step of
 //    the AR(p) model of a cascade level, bit-identical with the NumPy expression.
-// Everything is float64 like the reference; the reductions accumulate per block and are finished
-// by one block in a fixed order (deterministic, no atomics on values).
+// Everything is float64 like the reference.  The (mean, population std) of whole planes - level statistics,
+// field mean, the noise filter's standardisation - is psh::moments of noise_adj.hip: double-double sums of x
+// and x^2 with a zero shift, block partial sums finished by one block per plane in a fixed order
+// (deterministic, no atomics on values).  A plane that holds a NaN or an infinity gets a NaN std, like np.std.
 #include "common.h"
 
 extern "C" int psh_fft_rfft2_dev(const double *in_dev, int m, int n, void *out_dev);
@@ -24,69 +26,6 @@ namespace {
 
 constexpr int kRedBlocksF64 = 512;
 constexpr int kRedThreads = 256;
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
-// per plane p (gridDim.y): partial[p][block] = {sum, sum of squares} of (x - shift[p]); shift is a
-// device value per plane (nullptr: 0) that keeps the squares small (the level's first element)
-__global__ __launch_bounds__(kRedThreads) void moments_partial(const double *__restrict__ x, size_t plane,
-                                                               double2 *__restrict__ partial) {
-  __shared__ double2 s_part[kRedThreads / 64];
-  const double *src = x + static_cast<size_t>(blockIdx.y) * plane;
-  const double shift = src[0];
-  double s = 0.0, q = 0.0;
-  const size_t stride = static_cast<size_t>(gridDim.x) * kRedThreads;
-  for (size_t i = static_cast<size_t>(blockIdx.x) * kRedThreads + threadIdx.x; i < plane; i += stride) {
-    const double v = src[i] - shift;
-    s += v;
-    q += v * v;
-  }
-  s = wave_sum_f64(s);
-  q = wave_sum_f64(q);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = make_double2(s, q);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double2 t = s_part[0];
-    for (int w = 1; w < kRedThreads / 64; ++w) {
-      t.x += s_part[w].x;
-      t.y += s_part[w].y;
-    }
-    partial[static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x] = t;
-  }
-}
-
-// stats[p] = {mean, std} (population), one block per plane
-__global__ __launch_bounds__(kRedThreads) void moments_final(const double2 *__restrict__ partial, int nblocks,
-                                                             const double *__restrict__ x, size_t plane,
-                                                             double2 *__restrict__ stats) {
-  __shared__ double2 s_part[kRedThreads / 64];
-  const double2 *src = partial + static_cast<size_t>(blockIdx.x) * nblocks;
-  double s = 0.0, q = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += kRedThreads) {
-    s += src[i].x;
-    q += src[i].y;
-  }
-  s = wave_sum_f64(s);
-  q = wave_sum_f64(q);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = make_double2(s, q);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double2 t = s_part[0];
-    for (int w = 1; w < kRedThreads / 64; ++w) {
-      t.x += s_part[w].x;
-      t.y += s_part[w].y;
-    }
-    const double shift = x[static_cast<size_t>(blockIdx.x) * plane];
-    const double cnt = static_cast<double>(plane);
-    const double mean_shifted = t.x / cnt;
-    const double var = fmax(t.y / cnt - mean_shifted * mean_shifted, 0.0);
-    stats[blockIdx.x] = make_double2(mean_shifted + shift, sqrt(var));
-  }
-}
 
 // x[p] = (x[p] - mean[p]) / std[p], or x - mean only (centre_only)
 __global__ __launch_bounds__(kRedThreads) void standardise(double *__restrict__ x, size_t plane,
@@ -150,18 +89,6 @@ __global__ __launch_bounds__(kRedThreads) void ar_iterate(const double *__restri
 }
 
 }  // namespace
-
-// {mean, population std} of `planes` planes (declared in common.h: noise_adj.hip standardises with it too)
-int moments(const double *x_dev, int planes, size_t plane, double2 *stats_dev, hipStream_t stream) {
-  psh::Scratch partial;
-  if (int rc = partial.alloc(static_cast<size_t>(planes) * kRedBlocksF64 * sizeof(double2))) return rc;
-  hipLaunchKernelGGL(moments_partial, dim3(kRedBlocksF64, planes), dim3(kRedThreads), 0, stream, x_dev, plane,
-                     partial.as<double2>());
-  hipLaunchKernelGGL(moments_final, dim3(planes), dim3(kRedThreads), 0, stream, partial.as<const double2>(),
-                     kRedBlocksF64, x_dev, plane, stats_dev);
-  PSH_HIP(hipGetLastError());
-  return PSH_OK;
-}
 
 }  // namespace psh
 

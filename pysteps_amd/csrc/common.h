@@ -161,8 +161,9 @@ bool fft_shape_supported(int m, int n);
 int fft_irfft2_weighted(const void *spec_dev, const double *weights_dev, int m, int n, double *out_dev,
                         void *scratch_dev, unsigned long long *min_key_dev = nullptr);
 
-// {mean, population standard deviation} of each of `planes` float64 planes (cascade.hip): block partial sums finished
-// by one block per plane in a fixed order; queued on `stream`, stats_dev receives `planes` double2 (lock held)
+// {mean, population standard deviation} of each of `planes` (1..65535) float64 planes (noise_adj.hip): double-double
+// block partial sums finished by one block per plane in a fixed order; a non-finite plane gets a NaN std; queued on
+// `stream`, stats_dev receives `planes` double2 (lock held)
 int moments(const double *x_dev, int planes, size_t plane, double2 *stats_dev, hipStream_t stream);
 
 struct IdwArgs {

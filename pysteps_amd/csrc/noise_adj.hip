@@ -10,6 +10,7 @@
 //  * psh_mask_count_dev              - number of set bytes of a mask
 //  * psh_masked_moments_dev          - np.mean(x[mask]), np.std(x[mask]) of cascade/decomposition.py:223-228
 //  * psh_spectrum_level_moments_dev  - the unmasked level statistics read off the field's half spectrum
+//  * psh::moments                    - np.mean(x), np.std(x) of whole planes for cascade.hip and the prepare stage
 #include <algorithm>
 
 #include "common.h"
@@ -30,6 +31,10 @@ constexpr int kMaxLevels = 16;
 // hi + lo (Knuth's two-sum, the product's error from an fma): ~106 bits, the cancellation then costs nothing
 // that shows in a double, and the order of the additions stops mattering at the 1e-16 level.  The kernel is
 // bound by the planes' bytes, the extra flops are free.  The helpers are in dd.h.
+// The moments of whole planes (psh::moments below) are the same kernels without a mask.  They used to be plain
+// double sums of x - x[0]: fine while x[0] lies within a few standard deviations of the mean, but with
+// d = |x[0] - mean| / std the subtraction E[v^2] - E[v]^2 loses about d^2 of the significand (a rain cell on the
+// field's first pixel: d ~ sqrt(pixels)), and x - x[0] is itself rounded, so no shift taken from the data is exact.
 
 // one block's {sum, sum of squares} of a plane as four doubles
 struct Part {
@@ -66,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void masked_partial(const double *__restr
   for (int j = 0; j < P; ++j) acc[j] = {{0.0, 0.0}, {0.0, 0.0}};
   const size_t stride = static_cast<size_t>(gridDim.x) * kThreads;
   for (size_t i = static_cast<size_t>(blockIdx.x) * kThreads + threadIdx.x; i < plane; i += stride) {
-    if (!mask[i]) continue;
+    if (mask && !mask[i]) continue;  // no mask: every pixel (psh::moments)
 #pragma unroll
     for (int j = 0; j < P; ++j) {
       if (p0 + j < nplanes) {
@@ -83,10 +88,11 @@ __global__ __launch_bounds__(kThreads) void masked_partial(const double *__restr
   }
 }
 
-// stats[p] = {mean, population std} over `*count` pixels; one block per plane
+// stats[p] = {mean, population std} over `*count` pixels (count == nullptr: over `pixels`, the whole plane); one block
+// per plane.  A NaN in the plane leaves NaN in both (an infinity too: Inf - Inf in the two-sums), like np.std.
 __global__ __launch_bounds__(kThreads) void masked_final(const Part *__restrict__ partial, int nblocks,
                                                          const unsigned long long *__restrict__ count,
-                                                         double2 *__restrict__ stats) {
+                                                         unsigned long long pixels, double2 *__restrict__ stats) {
   __shared__ Part s_part[kThreads / 64];
   const Part *src = partial + static_cast<size_t>(blockIdx.x) * nblocks;
   Part acc = {{0.0, 0.0}, {0.0, 0.0}};
@@ -96,7 +102,7 @@ __global__ __launch_bounds__(kThreads) void masked_final(const Part *__restrict_
   }
   const Part t = block_sum(acc, s_part);
   if (threadIdx.x == 0) {
-    const double cnt = static_cast<double>(*count);  // 0: 0 / 0 = NaN, like NumPy on an empty selection
+    const double cnt = static_cast<double>(count ? *count : pixels);  // 0: 0 / 0 = NaN, like NumPy on an empty selection
     const dd mean = dd_div_d(t.s, cnt);
     const dd m2 = dd_sqr(mean);
     const dd ex2 = dd_div_d(t.q, cnt);
@@ -222,6 +228,23 @@ unsigned sweep_blocks(size_t n) {
 }
 
 }  // namespace
+
+// {mean, population std} of `planes` whole planes (declared in common.h; cascade.hip takes the level statistics, the
+// field mean and the noise filter's standardisation from it, psh_noise_adj_prepare_dev np.std(N)): the masked kernels
+// without a mask and with the plane's size for the count - one reduction, the same double-double sums in the same
+// fixed order.  A plane's pair depends on its own values alone, not on where in the plane they lie beyond rounding at
+// the 1e-16 level, nor on its neighbours or the number of planes.
+int moments(const double *x_dev, int planes, size_t plane, double2 *stats_dev, hipStream_t stream) {
+  Scratch partial;
+  if (int rc = partial.alloc(static_cast<size_t>(planes) * kPartBlocks * sizeof(Part))) return rc;
+  hipLaunchKernelGGL(masked_partial<1>, dim3(kPartBlocks, planes), dim3(kThreads), 0, stream, x_dev, planes, plane,
+                     static_cast<const unsigned char *>(nullptr), partial.as<Part>());
+  hipLaunchKernelGGL(masked_final, dim3(planes), dim3(kThreads), 0, stream, partial.as<const Part>(), kPartBlocks,
+                     static_cast<const unsigned long long *>(nullptr), static_cast<unsigned long long>(plane), stats_dev);
+  PSH_HIP(hipGetLastError());
+  return PSH_OK;
+}
+
 }  // namespace psh
 
 using psh::fail;
@@ -252,7 +275,7 @@ extern "C" int psh_noise_adj_prepare_dev(double *fields_dev, int nbatch, size_t 
   if (nbatch < 1 || nbatch > 65535 || plane == 0) return fail(PSH_EINVAL, "noise_adj_prepare: 1..65535 fields, not empty");
   psh::Scratch stats;
   if (int rc = stats.alloc(static_cast<size_t>(nbatch) * sizeof(double2))) return rc;
-  // np.std(N) of every realisation: the moments kernels the noise filter standardises with, per plane
+  // np.std(N) of every realisation: the reduction the noise filter standardises with, per plane
   if (int rc = psh::moments(fields_dev, nbatch, plane, stats.as<double2>(), c.stream)) return rc;
   if (stats_out_dev)
     PSH_HIP(hipMemcpyAsync(stats_out_dev, stats.as<void>(), static_cast<size_t>(nbatch) * sizeof(double2), hipMemcpyDeviceToDevice, c.stream));
@@ -288,7 +311,7 @@ extern "C" int psh_masked_moments_dev(const double *planes_dev, int nplanes, siz
     hipLaunchKernelGGL(psh::masked_partial<1>, dim3(psh::kPartBlocks, nplanes), dim3(psh::kThreads), 0, c.stream, planes_dev,
                        nplanes, plane, mask_dev, part);
   hipLaunchKernelGGL(psh::masked_final, dim3(nplanes), dim3(psh::kThreads), 0, c.stream, static_cast<const psh::Part *>(part),
-                     psh::kPartBlocks, count_dev, reinterpret_cast<double2 *>(stats_dev));
+                     psh::kPartBlocks, count_dev, 0ull, reinterpret_cast<double2 *>(stats_dev));
   PSH_HIP(hipGetLastError());
   return PSH_OK;
 }

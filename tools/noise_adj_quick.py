@@ -9,7 +9,9 @@ around each call, median and spread.
     chain and the hand-over of the generator states included (host work between the events shows up as device idle time
     inside them).
 (b) ``stages``: the pieces of one realisation - ``draw`` (all K white-noise fields in one launch, per call),
-    ``filter`` (psh_noise_filter_dev), ``prepare`` (one field), ``decompose_levels`` (L inverse transforms),
+    ``filter`` (psh_noise_filter_dev), ``prepare`` (one field), ``prepare_L_fields`` (a batch of L fields: the unmasked
+    moments of L whole planes - the reduction the cascade's level statistics and the noise filter share - plus the
+    element-wise pass, 8 + 16 bytes per pixel and plane), ``decompose_levels`` (L inverse transforms),
     ``masked_moments_ppb1`` / ``masked_moments_ppb4`` (L planes, one / four planes per block: the measurement behind
     ``PLANES_PER_BLOCK``), ``rfft2`` and ``spectrum_moments`` (the unconditional route), ``mask_count``.
 (c) ``reference_1024_s``: the reference's own function on the host at 1024^2 with the same levels and realisations, one
@@ -118,6 +120,11 @@ def draw():
 stages["seed_chain_handover_and_draw_%d_fields_ms" % K] = spread(timed(draw))
 stages["filter_ms"] = spread(timed(lambda: _lib.check(lib.psh_noise_filter_dev(white.view(0).ptr, d_filter.ptr, m, n, field.ptr), "filter")))
 stages["prepare_ms"] = spread(timed(lambda: adj.prepare(field, mask, 1.0, 0.0, THR2)))  # sigma 1, mu 0: the field keeps its scale
+batch = DeviceArray((L, m, n), np.float64)
+for k in range(L):
+    _lib.check(lib.psh_noise_filter_dev(white.view(k % K).ptr, d_filter.ptr, m, n, batch.view(k).ptr), "filter")
+stages["prepare_L_fields_ms"] = spread(timed(lambda: adj.prepare(batch, mask, 1.0, 0.0, THR2)))
+del batch
 stages["decompose_levels_ms"] = spread(timed(lambda: _lib.check(
     lib.psh_cascade_decompose_levels_dev(field.ptr, weights.ptr, L, m, n, levels.ptr), "levels")))
 for ppb in (1, 4):
