@@ -1145,6 +1145,13 @@ int psh_ssft_generate_dev(const double *white_dev, int K, int m, int n, const do
                           const long long *wins_host, int nwin, const double *tiles_dev, size_t tiles_count,
                           const double *sM_dev, double *out_dev);
 
+/* ---- aggregation, clipping and squaring of resident fields (csrc/dimension.hip) ----------------------------------- *
+ * pysteps/utils/dimension.py.  Declared in a header of its own, pysteps_hip_dimension.h, which is part of this one;
+ * the ctypes side keeps these entry points in a table of their own as well (pysteps_amd/_lib.py
+ * DIMENSION_SIGNATURES; tests/test_dimension_capi_cpu.py holds the two to each other and records what each entry
+ * point answers before the library is initialised). */
+#include "pysteps_hip_dimension.h"
+
 /* ---- multi-GPU: RCCL over xGMI, one rank (process) per GPU ------------------ *
  * The reference has no communication layer (single process, optional dask threads:
  * pysteps/nowcasts/utils.py:464-471); members / fields shard across GPUs with ONE

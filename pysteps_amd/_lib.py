@@ -247,6 +247,17 @@ SIGNATURES = {
     "psh_semilag_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int)]),
 }
 
+# The entry points of csrc/dimension.hip, declared in include/pysteps_hip_dimension.h (which pysteps_hip.h includes):
+# a table of their own, kept in step with that header by tests/test_dimension_capi_cpu.py.
+DIMENSION_SIGNATURES = {
+    "psh_aggregate_axis_dev": (c_int, [c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "psh_aggregate_space_dev": (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "psh_accumulate_step_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int]),
+    "psh_window_copy_dev": (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_int, c_double]),
+    "psh_field_min_dev": (c_int, [c_void_p, c_int, c_size_t, POINTER(c_double)]),
+}
+
 _lock = threading.RLock()
 _lib = None
 _initialised = False
@@ -268,7 +279,7 @@ def load():
             lib = ctypes.CDLL(LIB_PATH)
         except OSError as exc:
             raise HipLibraryError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(DIMENSION_SIGNATURES.items()):
             try:
                 fn = getattr(lib, name)
             except AttributeError as exc:

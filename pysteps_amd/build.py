@@ -39,7 +39,7 @@ def sources():
 
 
 def _deps():
-    return glob.glob(os.path.join(SRC_DIR, "*.h")) + [HEADER]
+    return glob.glob(os.path.join(SRC_DIR, "*.h")) + glob.glob(os.path.join(os.path.dirname(HEADER), "*.h"))
 
 
 DEBUG_LIB_PATH = os.path.join(LIB_DIR, "libpysteps_hip_debug.so")
