@@ -165,6 +165,10 @@ def test_lagrangian_probability_ndarray_timesteps(pysteps):
 
     table = extrapolation.interface._extrapolation_methods
     stock = table["semilagrangian"]
+    from pysteps.feature import interface as feat_if
+    from pysteps.postprocessing import interface as post_if
+
+    others = [(t, dict(t)) for t in (feat_if._detection_methods, post_if._ensemblestats_methods)]
     try:
         register.register(override=True)
         assert extrapolation.get_method("semilagrangian") is not stock
@@ -176,6 +180,8 @@ def test_lagrangian_probability_ndarray_timesteps(pysteps):
         from pysteps.motion.lucaskanade import dense_lucaskanade as stock_lk
 
         motion.interface._methods["lk"] = motion.interface._methods["lucaskanade"] = stock_lk
+        for other, before in others:  # the stock "blob", "shitomasi", "mean", "excprob", for the tests that run after this one
+            other.update(before)
     assert nan_mismatch(got, want) == 0
     assert rel_l2(got, want) < 1e-4
 
