@@ -170,26 +170,47 @@ def corner_min_eigenval(u8, block_size=5):
     return ((a + c) - np.sqrt((a - c) * (a - c) + b * b)).astype(np.float32)
 
 
-def good_features_to_track(u8, allowed, max_corners=1000, quality=0.01, min_distance=10, block_size=5):
-    """cv::goodFeaturesToTrack (featureselect.cpp), Shi-Tomasi variant.  Returns (p,2) float32 (x,y)."""
+def corner_candidates(u8, allowed, quality=0.01, block_size=5):
+    """The candidate stage of cv::goodFeaturesToTrack (featureselect.cpp): the response, its maximum over the
+    allowed pixels, threshold to zero, 3x3 dilate equality, != 0, the mask, the image border excluded.
+
+    Returns ``(eig, eig_max, keys)``: the float32 response plane as cornerMinEigenVal gives it, the float32 maximum
+    over the allowed pixels (-inf where nothing is allowed) and the candidates as uint64 keys, response bits << 32 |
+    y * n + x, in the order the walk takes them: descending value, ties by descending address (greaterThanPtr) -
+    which is descending key order, the responses of candidates being positive."""
     m, n = u8.shape
     eig = corner_min_eigenval(u8, block_size)
     if not allowed.any():
-        return np.empty((0, 2), dtype=np.float32)
+        return eig, np.float32(-np.inf), np.empty(0, dtype=np.uint64)
     max_val = eig[allowed].max()
     thr = np.float32(max_val * quality)
-    eig = np.where(eig > thr, eig, np.float32(0))            # THRESH_TOZERO
+    kept = np.where(eig > thr, eig, np.float32(0))            # THRESH_TOZERO
     pad = np.full((m + 2, n + 2), -np.inf, dtype=np.float32)  # dilate: border neutral
-    pad[1:-1, 1:-1] = eig
+    pad[1:-1, 1:-1] = kept
     dil = np.max([pad[i:i + m, j:j + n] for i in range(3) for j in range(3)], axis=0)
-    cand = (eig != 0) & (eig == dil) & allowed
+    cand = (kept != 0) & (kept == dil) & allowed
     cand[0, :] = cand[-1, :] = False
     cand[:, 0] = cand[:, -1] = False
     ys, xs = np.nonzero(cand)
-    vals = eig[ys, xs]
-    # descending value, ties by descending address (greaterThanPtr)
+    vals = kept[ys, xs]
     order = np.lexsort((-(ys * n + xs), -vals.astype(np.float64)))
-    ys, xs = ys[order], xs[order]
+    ys, xs, vals = ys[order], xs[order], np.ascontiguousarray(vals[order])
+    keys = (vals.view(np.uint32).astype(np.uint64) << np.uint64(32)) | (ys * n + xs).astype(np.uint64)
+    return eig, max_val, keys
+
+
+def good_features_to_track(u8, allowed, max_corners=1000, quality=0.01, min_distance=10, block_size=5):
+    """cv::goodFeaturesToTrack (featureselect.cpp), Shi-Tomasi variant.  Returns (p,2) float32 (x,y)."""
+    m, n = u8.shape
+    _, _, keys = corner_candidates(u8, allowed, quality, block_size)
+    return walk_candidates(keys, m, n, max_corners, min_distance)
+
+
+def walk_candidates(keys, m, n, max_corners=1000, min_distance=10):
+    """The walk of cv::goodFeaturesToTrack over the candidates in the order given: a candidate is accepted unless an
+    accepted corner lies closer than ``min_distance``.  Returns (p,2) float32 (x,y)."""
+    addr = (np.asarray(keys, dtype=np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    ys, xs = addr // n, addr % n
     if min_distance < 1:
         sel = slice(None, max_corners if max_corners > 0 else None)
         return np.column_stack([xs[sel], ys[sel]]).astype(np.float32)

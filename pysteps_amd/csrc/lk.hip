@@ -816,8 +816,11 @@ __global__ __launch_bounds__(256) void lk_corner_response_cols(
     const float sx = neg_x ? -s : s, sx2 = neg_x ? -s2 : s2;
     const unsigned char *col = u8 + reflect101(xl, n);
     // rows are reflected at most once unless the image is only a few rows high (scalar arithmetic per
-    // row: keep the division of the general form out of the walk)
-    const bool few_rows = m < 2 * H + 2;
+    // row: keep the division of the general form out of the walk).  The walk itself reaches row m + r; the preload
+    // below runs up to BS rows ahead of the last product row, as far as row m + 3 BS - r - 2, and a single reflection
+    // of that row, 2 m - 2 - y, has to stay in the image as well: m >= 3 BS - r
+    constexpr int kFewRows = 2 * H + 2 > 3 * BS - r ? 2 * H + 2 : 3 * BS - r;
+    const bool few_rows = m < kFewRows;
     auto row_of = [&](int y) -> int {
       if (few_rows) return reflect101(y, m);
       y = y < 0 ? -y : y;
@@ -850,7 +853,7 @@ __global__ __launch_bounds__(256) void lk_corner_response_cols(
     for (int base = 1; base <= last_p; base += BS) {
       int nxt[BS];
 #pragma unroll
-      for (int j = 0; j < BS; ++j) nxt[j] = load_row(base + BS + 1 + j);  // (reflected: always inside the image)
+      for (int j = 0; j < BS; ++j) nxt[j] = load_row(base + BS + 1 + j);  // (inside the image: see kFewRows)
 #pragma unroll
       for (int j = 0; j < BS; ++j) {
         const int p = base + j;
@@ -973,7 +976,9 @@ __global__ __launch_bounds__(256) void lk_corner_response_nms(
     const bool neg_x = walk_mirrored(xl + 1, n);
     const float sx = neg_x ? -s : s, sx2 = neg_x ? -s2 : s2;
     const unsigned char *col = u8 + reflect101(xl, n);
-    const bool few_rows = m < 2 * H + 4;
+    // (the preload reaches row m + 3 BS - r - 1 here: one response row more than lk_corner_response_cols)
+    constexpr int kFewRows = 2 * H + 4 > 3 * BS - r + 1 ? 2 * H + 4 : 3 * BS - r + 1;
+    const bool few_rows = m < kFewRows;
     auto row_of = [&](int y) -> int {
       if (few_rows) return reflect101(y, m);
       y = y < 0 ? -y : y;
@@ -2278,8 +2283,11 @@ struct CornerWs {
     nb = rgrid.x * rgrid.y;
     // every pixel can be a candidate (plateaus of equal response pass the 3x3 test): no overflow
     cap = static_cast<int>(std::min<size_t>(npx, 0x7fffffffu));
-    // ... and the fused response pass gives every wave of its grid kNmsKeys slots (tiny images: more slots than pixels)
-    cap = std::max(cap, psh::lk_response_nms_fixed_keys(psh::lk_response_nms_grid(m, n, block_size)));
+    // ... and the fused response pass gives every wave of its grid kNmsKeys slots, used or not, and appends what a
+    // wave cannot hold BEHIND all of them: the fixed slots come on top of the pixels (on a plateau image of a few rows
+    // the spilled keys alone outnumber the pixels that max(pixels, slots) left for them, and the pass dropped them)
+    cap = static_cast<int>(std::min<size_t>(
+        static_cast<size_t>(cap) + psh::lk_response_nms_fixed_keys(psh::lk_response_nms_grid(m, n, block_size)), 0x7fffffffu));
     auto up = [](size_t v) { return (v + 255) & ~static_cast<size_t>(255); };
     off_part = up(npx * sizeof(float));
     off_cnt = up(off_part + static_cast<size_t>(nb) * sizeof(float));

@@ -127,7 +127,7 @@ def _corner_candidates(bf, block_size, quality_level):
     s = bf.stats.to_host()
     s[_EIG_MAX] = (yield ("allreduce", s[_EIG_MAX:_EIG_MAX + 1], "max"))[0]
     bf._put_stats(s)
-    cap = max((r1 - r0) * bf.n // 6 + 4096, 4096)
+    cap = max((r1 - r0) * bf.n, 1)  # every pixel can be a candidate: plateaus of equal response pass the 3x3 test
     keys = DeviceArray((cap,), np.uint64)
     count = DeviceArray((1,), np.int32)
     _lib.check(lib.psh_lk_band_select_dev(eig.ptr, bf.clean.ptr, bf.m, bf.n, e0, e1, r0, r1, bf.buffer_mask,
@@ -135,7 +135,9 @@ def _corner_candidates(bf, block_size, quality_level):
     found = int(count.to_host()[0])
     if found > cap:
         raise RuntimeError("corner candidates of the band exceed the buffer (%d > %d)" % (found, cap))
-    return keys.to_host()[:found].copy()
+    if found == 0:
+        return np.empty(0, np.uint64)
+    return DeviceArray((found,), np.uint64, ptr=keys.ptr, owner=keys).to_host().copy()  # only the keys written
 
 
 class _BandPyramid:
